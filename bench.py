@@ -9,6 +9,13 @@ the records already resident in HBM.  Weak scaling: every rank aggregates its ow
 all-reduce (the per-scrape-epoch merge).
 
     python bench.py [--gpus N --steps K --warmup W --config c2 --records R]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs: set-up, settle + warm-up, the timed steps,
+the result line.  --dump-outputs DIR also writes the state the timed steps left (the series a
+scrape would return, the sketches) as DIR/<name>.npy.  --full adds every other measurement
+and check: the scrape cost, the Go-batch-size launches, the host-fed rates, the CPU baseline,
+--check-merge and --production-only.
 
 Other BASELINE.json configs (parity-test cases; bench lines under profiles/):
   --config c3   2^27 records per GPU (2^30 on 8 GPUs), C2 metrics + count-min
@@ -511,6 +518,52 @@ def merge_check(args, cfg, spec, sketch, remote, n, world, g, gen, cols_of, pods
         ref.close()
 
 
+DUMP_MAX_SERIES = 1 << 21   # series values + key hashes: 2 x 16 MiB of float64 at the most
+DUMP_MAX_CMS = 1 << 22      # count-min counters: 32 MiB of float64 (C3's d=4, w=2^20 whole)
+DUMP_MAX_HLL = 1 << 21      # HLL registers: 8 MiB of float32
+DUMP_SEED = 20240607
+
+
+def _dump_sample(a: np.ndarray, limit: int) -> np.ndarray:
+    """`a` flattened; above `limit` elements a fixed, seeded sample of them in index order
+    (the same indices for the same size, whichever build produced the values)."""
+    a = a.reshape(-1)
+    if a.size <= limit:
+        return a
+    idx = np.random.default_rng(DUMP_SEED).choice(a.size, limit, replace=False)
+    idx.sort()
+    return a[idx]
+
+
+def dump_outputs(g, out_dir: str, sketch) -> dict:
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the
+    engine's snapshot (every series of the scrape) and, with sketches, the count-min counters
+    and HLL registers -- as float .npy files.  The engine was reset after the warm-up, so the
+    state is exactly the timed steps over the seeded workload: two builds run with the same
+    arguments write comparable files.
+      series_values.npy  float64: the series' values (exact: uint64 below 2^53), ordered by
+                         (metric, labels)
+      series_keys.npy    float64: CRC-32 of each series' "metric{name=value,...}" text, same order
+      cms.npy            float64: count-min counters, row-major [depth, width]
+      hll.npy            float32: HLL registers, row-major [slots, 2^p]"""
+    import zlib
+    os.makedirs(out_dir, exist_ok=True)
+    snap = g.snapshot()
+    keys = sorted(snap)
+    vals = np.fromiter((snap[k] for k in keys), np.float64, len(keys))
+    crcs = np.fromiter((zlib.crc32(("%s{%s}" % (m, ",".join("%s=%s" % lv for lv in labels))).encode())
+                        for m, labels in keys), np.float64, len(keys))
+    arrays = {"series_values": _dump_sample(vals, DUMP_MAX_SERIES),
+              "series_keys": _dump_sample(crcs, DUMP_MAX_SERIES)}
+    if sketch:
+        arrays["cms"] = _dump_sample(g.cms_array(), DUMP_MAX_CMS).astype(np.float64)
+        arrays["hll"] = _dump_sample(g.hll_array(), DUMP_MAX_HLL).astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "series": len(keys),
+            "files": {name + ".npy": [int(a.size), str(a.dtype)] for name, a in arrays.items()}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=0,
@@ -523,9 +576,17 @@ def main():
     ap.add_argument("--cpu-backend", action="store_true",
                     help="run the engine's CPU backend (GPUAGG_FLAG_CPU_BACKEND, host memory) instead of "
                          "a GPU: rehearses the multi-rank path on a machine without one (not a bench line)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run every measurement and check beside the headline "
+                         "figure: scrape cost, Go-batch-size launches, host-fed rates, CPU baseline (each has "
+                         "its --no-* switch); --check-merge and --production-only need it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="reset the engines after the warm-up, and after the timed region write rank 0's "
+                         "state (series values and key hashes; count-min and HLL with sketches) as "
+                         "DIR/<name>.npy")
     ap.add_argument("--check-merge", action="store_true",
-                    help="reset the engines after the warm-up, and after the timed region check rank 0's "
-                         "merged state against one engine fed every rank's batch")
+                    help="(--full) reset the engines after the warm-up, and after the timed region check "
+                         "rank 0's merged state against one engine fed every rank's batch")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="c2")
@@ -534,13 +595,13 @@ def main():
                     help="records in the tuned CPU baseline sample (go-shaped: 1/8 of it)")
     ap.add_argument("--settle-ms", type=float, default=40.0,
                     help="untimed passes of the step for this long before the warm-up steps (clock settle)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-fed", action="store_true")
-    ap.add_argument("--no-scrape", action="store_true", help="skip the snapshot / render timing")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-host-fed", action="store_true", help="(--full) skip the host-fed rates")
+    ap.add_argument("--no-scrape", action="store_true", help="(--full) skip the snapshot / render timing")
     ap.add_argument("--production-only", action="store_true",
-                    help="diagnostic: only the production-geometry launches (for rocprof), no bench line")
+                    help="(--full) diagnostic: only the production-geometry launches (for rocprof), no bench line")
     ap.add_argument("--no-production", action="store_true",
-                    help="skip the Go-batch-size (1M-record) device-resident launches")
+                    help="(--full) skip the Go-batch-size (1M-record) device-resident launches")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -551,6 +612,8 @@ def main():
         raise SystemExit("bench.py: --gpus %d but WORLD_SIZE=%d" % (args.gpus, world))
     if args.cpu_backend and args.backend != "gloo":
         raise SystemExit("bench.py: --cpu-backend merges over gloo (pass --backend gloo)")
+    if (args.check_merge or args.production_only) and not args.full:
+        raise SystemExit("bench.py: --check-merge and --production-only are not part of a plain run (pass --full)")
     if args.check_merge and args.config == "c5":
         # DNS ids index each rank's own generated payload dictionary; the merge of DNS keys
         # needs one dictionary interned alike on every rank (as the Go plugin does per context)
@@ -644,7 +707,7 @@ def main():
     g.sync()
     if world > 1:  # an untimed merge first: RCCL communicators and merge buffers exist before the clock
         merge_engine(g)
-    if args.check_merge:  # the state then holds exactly the timed steps
+    if args.check_merge or args.dump_outputs:  # the state then holds exactly the timed steps
         g.reset()
 
     # ---- timed region --------------------------------------------------------------
@@ -741,14 +804,17 @@ def main():
     if args.check_merge and rank == 0:
         result["merge_check"] = merge_check(args, cfg, spec, sketch, remote, n, world, g, gen, cols_of, pods,
                                             gen_kw, chunk, capacity)
-    if rank == 0 and not args.no_scrape:
+    if args.dump_outputs and rank == 0:  # before anything below adds to the engine's state
+        result["outputs"] = dump_outputs(g, args.dump_outputs, sketch)
+    full = args.full  # everything below: measurements and checks beside the headline figure
+    if full and rank == 0 and not args.no_scrape:
         result["scrape"] = scrape_cost(g)
-    if rank == 0 and world == 1 and not cpu and not args.no_production and n > GO_BATCH:
+    if full and rank == 0 and world == 1 and not cpu and not args.no_production and n > GO_BATCH:
         result["production"] = production_geometry(g, cols, n, bpr, stats["kernel_ms"] / max(1, stats["kernel_launches"]))
-    if rank == 0 and world == 1 and not cpu and not args.no_host_fed:
+    if full and rank == 0 and world == 1 and not cpu and not args.no_host_fed:
         result["host_fed"] = host_fed_rate(g, cols, n, args.steps)
         result["host_fed_raw"] = host_fed_raw_rate(g, pods, spec, cfg["seed"] + 17)
-    if rank == 0 and world == 1 and not cpu and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not cpu and not args.no_cpu_baseline:
         go_s, tu_s = (400_000, 4_000_000) if args.config == "c5" else (args.cpu_sample // 8, args.cpu_sample)
         result["cpu_baseline"] = cpu_baseline(args.config, pods, spec, cfg["seed"], gen_kw, go_s, tu_s,
                                               remote=remote)

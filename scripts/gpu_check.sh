@@ -35,7 +35,7 @@ for s in $STEPS; do
     smoke)
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/${TAG}_smoke.log" 2>&1 || exit $? ;;
     bench)
-      timeout -k 10 600 python bench.py --config "$cfg" > "$OUT/${TAG}_bench_${cfg}.json" 2> "$OUT/${TAG}_bench_${cfg}.err"
+      timeout -k 10 600 python bench.py --config "$cfg" --full > "$OUT/${TAG}_bench_${cfg}.json" 2> "$OUT/${TAG}_bench_${cfg}.err"
       rc=$?; echo "bench rc=$rc" >> "$OUT/${TAG}_bench_${cfg}.err"; [ $rc -ne 0 ] && exit $rc ;;
     prof)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_prof_${cfg}" -o run \
@@ -44,9 +44,9 @@ for s in $STEPS; do
       rc=$?; echo "prof rc=$rc" >> "$OUT/${TAG}_prof_${cfg}.log"; [ $rc -ne 0 ] && exit $rc
       find "$OUT/${TAG}_prof_${cfg}" -name "*kernel_stats.csv" -exec cp {} "$OUT/${TAG}_${cfg}_kernel_stats.csv" \; ;;
     pprof)
-      # the production-geometry launches alone (bench.py --production-only)
+      # the production-geometry launches alone (bench.py --full --production-only)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_pprof_${cfg}" -o run \
-        -- python3 "$R/bench.py" --config "$cfg" --production-only > "$OUT/${TAG}_pprof_${cfg}.log" 2>&1
+        -- python3 "$R/bench.py" --config "$cfg" --full --production-only > "$OUT/${TAG}_pprof_${cfg}.log" 2>&1
       rc=$?; echo "pprof rc=$rc" >> "$OUT/${TAG}_pprof_${cfg}.log"; [ $rc -ne 0 ] && exit $rc
       find "$OUT/${TAG}_pprof_${cfg}" -name "*kernel_stats.csv" -exec cp {} "$OUT/${TAG}_${cfg}_pprof_kernel_stats.csv" \; ;;
     pmc)

@@ -36,7 +36,7 @@ def _line(p):
 @pytest.mark.parametrize("config,records", [("c3", 200_000), ("c4-remote", 200_000)])
 def test_two_rank_cpu_backend_merge(config, records):
     p = _run(["--gpus", "2", "--backend", "gloo", "--cpu-backend", "--config", config, "--records", str(records),
-              "--steps", "2", "--warmup", "1", "--check-merge", "--settle-ms", "0", "--no-scrape"])
+              "--steps", "2", "--warmup", "1", "--full", "--check-merge", "--settle-ms", "0", "--no-scrape"])
     d = _line(p)
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["steps"] == 2
     assert d["config"]["parallelism"].startswith("dp2")
@@ -46,6 +46,31 @@ def test_two_rank_cpu_backend_merge(config, records):
     if config == "c3":
         assert mc["cms_equal"] and mc["hll_equal"]
     assert d["merge_ms"] is not None and d["merge_ms"] > 0
+
+
+def test_dump_outputs_repeatable_and_plain_run_lean(tmp_path):
+    """--dump-outputs writes the state of exactly the timed steps (however many settle passes
+    ran before them) as float arrays; a run without --full carries no side measurement."""
+    import numpy as np
+    base = ["--gpus", "1", "--backend", "gloo", "--cpu-backend", "--config", "c3", "--records", "50000",
+            "--steps", "2", "--warmup", "1"]
+    lines = [_line(_run(base + ["--settle-ms", ms, "--dump-outputs", str(tmp_path / d)]))
+             for d, ms in (("a", "0"), ("b", "40"))]
+    for d in lines:
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        assert not {"scrape", "production", "host_fed", "host_fed_raw", "cpu_baseline", "merge_check"} & set(d)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["cms.npy", "hll.npy", "series_keys.npy", "series_values.npy"]
+    total = 0
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and a.size > 0
+        assert np.array_equal(a, b), f
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "cms.npy").sum() == 2 * 4 * 50000  # 2 steps, depth 4, every record
+    p = _run(base + ["--check-merge"])
+    assert p.returncode != 0 and "--full" in p.stderr
 
 
 def test_world_mismatch_refused():
@@ -70,7 +95,7 @@ def test_rank_device_mapping():
 def test_two_rank_gpu_bench_merge(gpu_device):
     """The driver's scaling command shape on one GPU: two gfx950 ranks (gloo, sharing cuda:0)."""
     p = _run(["--gpus", "2", "--backend", "gloo", "--config", "c3", "--records", "2000000", "--steps", "3",
-              "--warmup", "1", "--check-merge", "--settle-ms", "0", "--no-scrape"], timeout=300)
+              "--warmup", "1", "--full", "--check-merge", "--settle-ms", "0", "--no-scrape"], timeout=300)
     d = _line(p)
     assert d["n_gpus"] == 2 and d["value"] > 0
     assert d["merge_check"]["equal"], d["merge_check"]
