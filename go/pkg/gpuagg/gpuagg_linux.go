@@ -73,7 +73,12 @@ const (
 	flushInterval = 100 * time.Millisecond
 	scrapeEpoch   = 5 * time.Second
 	maxSlots      = 1 << 20 // hard cap; dense counters grow with the pods actually seen
-	sparseLog2    = 22
+	// Group-by table per device: 2^20 slots (42 MB) to start with, grown on demand
+	// (gpuagg_set_sparse_growth) up to 2^26 slots x 40 B = 2.7 GB, about 4 GB while the old
+	// and the new table coexist during a grow; the overflow list is the library's default
+	// (2^22 entries, 160 MiB: one launch of packetCapacity samples at one update each).
+	sparseLog2    = 20
+	sparseMaxLog2 = 26
 	channelDepth  = 10000 // like packetparser's recordsChannel (types_linux.go:37-38)
 	pieceDepth    = 16    // full pieces of rawPiece waiting for Start (1M samples)
 )
@@ -175,6 +180,7 @@ type gpuAgg struct {
 	latency    *latencyCollector
 	noResponse *prometheus.CounterVec
 	noRespLast float64
+	lostLast   uint64 // gpuagg_result_dropped of the previous publish (cumulative since reset)
 }
 
 type dnsPayload struct {
@@ -382,6 +388,11 @@ func (g *gpuAgg) Init() error {
 		if rc := C.gpuagg_create(&cfg, &d.ctx); rc != C.GPUAGG_OK {
 			g.destroyLocked()
 			return fmt.Errorf("gpuagg_create(device %d): %d", dev, int(rc))
+		}
+		if err := check(d.ctx, C.gpuagg_set_sparse_growth(d.ctx, sparseMaxLog2, 0), "gpuagg_set_sparse_growth"); err != nil {
+			C.gpuagg_destroy(d.ctx)
+			g.destroyLocked()
+			return err
 		}
 		if err := check(d.ctx, C.gpuagg_alloc_batch(d.ctx, batchCapacity, &d.batch), "gpuagg_alloc_batch"); err != nil {
 			C.gpuagg_destroy(d.ctx)
@@ -906,9 +917,21 @@ func (g *gpuAgg) publish() error {
 		return err
 	}
 	defer C.gpuagg_result_free(r)
-	if lost := uint64(C.gpuagg_result_dropped(r)); lost > 0 {
+	lost := uint64(C.gpuagg_result_dropped(r))
+	if lost > 0 {
 		g.l.Warn("group-by table full: series undercount", zap.Uint64("lost_updates", lost))
+		// the reference counts what it loses in LostEventsCounter (metrics_module.go:298-301):
+		// the updates lost since the previous publish (the engine's count is cumulative and
+		// restarts at a reset, e.g. the non-target side of a merge: then the whole value is new)
+		delta := lost
+		if lost >= g.lostLast {
+			delta = lost - g.lostLast
+		}
+		if delta > 0 {
+			metrics.LostEventsCounter.WithLabelValues(utils.BufferedChannel, name).Add(float64(delta))
+		}
 	}
+	g.lostLast = lost
 	n := int(C.gpuagg_result_count(r))
 	// counter series of this snapshot: what was already added per label tuple.  Tuples
 	// missing from the snapshot are dropped (their slots were retired), and a value below

@@ -58,7 +58,9 @@ typedef struct gpuagg_config {
                                     0 = local context, 1 = remote context            */
   uint32_t max_slots;            /* endpoint identity slots (pods), <= 2^21-2        */
   uint32_t max_ips;              /* pod IPs in the IP table                          */
-  uint32_t sparse_capacity_log2; /* group-by hash table entries = 2^this (0: 22)     */
+  uint32_t sparse_capacity_log2; /* group-by hash table entries = 2^this (0: 22); the
+                                    initial size when growth is on
+                                    (gpuagg_set_sparse_growth)                        */
   uint32_t cms_depth;            /* count-min rows (0 = sketches off)                */
   uint32_t cms_width_log2;       /* count-min columns = 2^this                       */
   uint32_t hll_precision;        /* HyperLogLog p (registers 2^p per source pod; 0=off) */
@@ -91,7 +93,33 @@ typedef struct gpuagg_config {
                                           have no port / DNS fields: measured C1 -3 %, C4 remote +6 %
                                           per step (the entries are written as partial sectors)   */
 
+#define GPUAGG_FLAG_REGROW_DIRECT 1024u /* a growing group-by table is rebuilt with memory-side atomics at
+                                          every size, not one LDS-built segment per workgroup
+                                          (diagnostics / tests) */
+
 int gpuagg_create(const gpuagg_config *cfg, gpuagg_ctx **out);
+/* Growth of the group-by table (off by default: the table keeps 2^sparse_capacity_log2
+ * entries and a full probe segment loses the update).  With max_log2 != 0 an update that
+ * finds its segment full is kept in an overflow list of overflow_entries entries (0: 2^22,
+ * 40 bytes each), and the table is rebuilt at a larger size -- up to 2^max_log2 entries,
+ * the list inserted again -- when the list holds entries or the table is more than half
+ * full: at gpuagg_sync, every state read, export, import and merge, and between syncs
+ * before a submit once an earlier submit has used the list (no wait, no extra
+ * synchronisation while it is empty).  Series are then exact unless more than
+ * overflow_entries updates overflow between two such points or the table has reached
+ * 2^max_log2 (gpuagg_result_dropped).  sparse_capacity_log2 <= max_log2 <= 30, else
+ * GPUAGG_EINVAL; max_log2 == 0 turns growth off again (the table keeps its size; it never
+ * shrinks, also not at gpuagg_reset / gpuagg_reconcile).  Legal any time after
+ * gpuagg_create.  If a larger table cannot be allocated the call that tried returns
+ * GPUAGG_ENOMEM and nothing is lost: the old table and the list stay. */
+int gpuagg_set_sparse_growth(gpuagg_ctx *ctx, uint32_t max_log2, uint32_t overflow_entries);
+/* The table's current size (log2 of its entries), the rebuilds at a larger size and the
+ * overflow entries inserted again since gpuagg_create (any pointer may be NULL). */
+int gpuagg_sparse_info(gpuagg_ctx *ctx, uint32_t *capacity_log2, uint64_t *grows, uint64_t *overflow_replayed);
+/* What rebuilt the table at the last grow: "sparse_regrow_kernel" (one LDS-built segment per
+ * workgroup), "sparse_rehash_direct_kernel" (memory-side atomics: tables beyond 2^24 wide /
+ * 2^25 compact entries, GPUAGG_FLAG_REGROW_DIRECT) or "cpu"; "" before the first grow. */
+const char *gpuagg_regrow_kernel_name(const gpuagg_ctx *ctx);
 /* Number of gfx950 devices visible to this process (one ctx per device). */
 int gpuagg_device_count(int *n);
 void gpuagg_destroy(gpuagg_ctx *ctx);
@@ -373,7 +401,11 @@ int gpuagg_result_series(const gpuagg_result *r, size_t i, const char **metric,
  * prometheusexporter.go:46-66). */
 int gpuagg_result_family(const gpuagg_result *r, size_t i, const char **type, const char **help);
 /* Group-by updates lost to a full table since the last reset (0 = every series exact).
- * The snapshot still succeeds; series of the lost updates undercount. */
+ * The snapshot still succeeds; series of the lost updates undercount.  With growth on
+ * (gpuagg_set_sparse_growth) only updates that arrive after the table has reached
+ * 2^max_log2 entries and their segment is full, or after the overflow list has filled,
+ * are lost.  An entry is counted with its count: an imported or replayed entry of count c
+ * that finds no slot is c lost updates. */
 uint64_t gpuagg_result_dropped(const gpuagg_result *r);
 /* Renders the series in the Prometheus text exposition format (0.0.4) exactly as
  * client_golang's registry Gather + expfmt would for the AdvancedRegistry: families
@@ -525,7 +557,8 @@ typedef struct gpuagg_stats {
   uint64_t records;          /* rows submitted                                   */
   uint64_t batches;          /* batches submitted                                */
   uint64_t sparse_entries;   /* occupied group-by table entries (at last sync)   */
-  uint64_t sparse_dropped;   /* updates lost to a full group-by table (at sync)  */
+  uint64_t sparse_dropped;   /* updates lost to a full group-by table (at sync); growth on:
+                                to a full table at its maximum size or a full overflow list */
   uint64_t kernel_launches;  /* timed aggregation launches                       */
   double kernel_ms;          /* summed device time of the aggregation kernel (HIP events) */
   double fold_ms;            /* summed device time of the spill fold kernel          */

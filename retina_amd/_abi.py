@@ -36,6 +36,7 @@ FLAG_NO_WIDE_LISTS = 32  # diagnostics: wide group-by keys with memory-side atom
 FLAG_CPU_BACKEND = 128  # host threads and host memory instead of a device (GPUAGG_FLAG_CPU_BACKEND)
 FLAG_ROW_RADIX = 256  # diagnostics: radix LDS IP images with the row table even when dense ones fit
 FLAG_NARROW_ENTRIES = 512  # 24-byte wide-list entries when the plan's keys have no port / DNS fields
+FLAG_REGROW_DIRECT = 1024  # diagnostics: a growing group-by table is rebuilt with memory-side atomics
 
 
 class MetricOptions(C.Structure):
@@ -135,6 +136,9 @@ SIGNATURES = [
     ("gpuagg_state", C.c_int, [C.c_void_p, C.POINTER(StateDesc)]),
     ("gpuagg_sparse_export", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("gpuagg_sparse_import", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    ("gpuagg_set_sparse_growth", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("gpuagg_sparse_info", C.c_int, [C.c_void_p, u32p, u64p, u64p]),
+    ("gpuagg_regrow_kernel_name", C.c_char_p, [C.c_void_p]),
     ("gpuagg_get_stats", C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     ("gpuagg_set_timing", C.c_int, [C.c_void_p, C.c_int]),
     ("gpuagg_stream", C.c_void_p, [C.c_void_p]),

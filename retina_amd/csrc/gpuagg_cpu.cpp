@@ -158,6 +158,24 @@ void apply_groups(const Plan &p, D &&dense, S &&sparse, uint32_t sip, uint32_t d
   }
 }
 
+// sparse_full of gpuagg_kernels.hip: a full segment's update goes to the overflow list
+// (growth mode) and is lost only when the list cannot take it.
+void table_full(const SparseView &s, uint64_t k0, uint64_t k1, uint64_t k2, uint64_t c, uint64_t b) {
+  if (s.overflow) {
+    const uint64_t pos = s.overflow[0]++;
+    if (pos < s.overflow[1]) {
+      uint64_t *e = s.overflow + kOverflowHeaderWords + pos * kSparseEntryWords;
+      e[0] = k0;
+      e[1] = k1;
+      e[2] = k2;
+      e[3] = c;
+      e[4] = b;
+      return;
+    }
+  }
+  *s.dropped += c;
+}
+
 // sparse_add / sparse_add_compact of gpuagg_kernels.hip on host memory (one writer:
 // flush() runs single-threaded).
 void table_add(const SparseView &s, uint64_t k0, uint64_t k1, uint64_t k2, uint64_t c, uint64_t b) {
@@ -173,7 +191,7 @@ void table_add(const SparseView &s, uint64_t k0, uint64_t k1, uint64_t k2, uint6
         return;
       }
     }
-    *s.dropped += c;
+    table_full(s, key & 0xFFFFFFFF00000000ULL, 0, key & 0xFFFFFFFFULL, c, 0);  // as sparse_export expands it
     return;
   }
   const uint32_t h0 = (uint32_t)key_hash(k0, k1, k2) & s.mask, smask = (1u << s.seg_log2) - 1u;
@@ -194,7 +212,7 @@ void table_add(const SparseView &s, uint64_t k0, uint64_t k1, uint64_t k2, uint6
       return;
     }
   }
-  *s.dropped += c;
+  table_full(s, k0, k1, k2, c, b);
 }
 
 // Splits [0, n) over the engine's threads.
@@ -556,6 +574,26 @@ void sparse_import(const SparseView &v, const uint64_t *in, size_t n) {
     const uint64_t *e = in + i * kSparseEntryWords;
     table_add(v, e[0], e[1], e[2], e[3], e[4]);
   }
+}
+
+// A plain rehash of every occupied slot into the larger, initialised table.
+void sparse_regrow(const SparseView &old, size_t old_slots, const SparseView &neu) {
+  for (size_t i = 0; i < old_slots; ++i) {
+    if (old.compact) {
+      const uint64_t key = old.k0[2 * i];
+      if (key) table_add(neu, key & 0xFFFFFFFF00000000ULL, 0, key & 0xFFFFFFFFULL, old.k0[2 * i + 1], 0);
+      continue;
+    }
+    const uint64_t *w = old.k0 + i * kSparseSlotWords;
+    if (w[0]) table_add(neu, w[0], w[1], w[2], w[3], w[4]);
+  }
+}
+
+size_t sparse_occupied(const SparseView &v, size_t slots) {
+  const size_t stride = v.compact ? 2 : kSparseSlotWords;
+  size_t n = 0;
+  for (size_t i = 0; i < slots; ++i) n += v.k0[i * stride] != 0;
+  return n;
 }
 
 void zero_slots(uint64_t *cnt, uint64_t *byt, uint8_t *hll, uint32_t hll_p, const uint32_t *dead, uint32_t ndead,

@@ -380,6 +380,19 @@ GA_HD uint64_t wide_pack12(uint64_t k1, uint64_t k2) { return ((k1 >> 9) << 32) 
 GA_HD uint64_t wide_unpack1(uint64_t n) { return (n >> 32) << 9; }
 GA_HD uint64_t wide_unpack2(uint64_t n) { return (n & 0xFFFFFFFFULL) << 32; }
 constexpr int kSparseEntryWords = 5;  // k0 k1 k2 count bytes
+// Overflow list of the growth mode (gpuagg_set_sparse_growth): one u64 array, word 0 the fill
+// counter (it keeps counting past the capacity), word 1 the capacity in entries, entries
+// of kSparseEntryWords words from word kOverflowHeaderWords on.  An update that finds its
+// segment full is appended there instead of being lost; the host grows the table and
+// inserts the list again (settle_sparse, gpuagg_runtime.cpp).
+constexpr uint32_t kOverflowHeaderWords = 8;
+constexpr uint64_t kOverflowDefaultEntries = 1ull << 22;
+// words of the block SparseView::dropped points at: lost updates; the overflow fill and the
+// occupied slots (written by sparse_count_kernel for the host's one readback); the device
+// address of the overflow list, 0 when there is none or the table cannot grow any more
+// (written by the host, read by a kernel only where it would otherwise lose an update)
+constexpr uint32_t kSparseWordDropped = 0, kSparseWordFill = 1, kSparseWordOccupied = 2, kSparseWordOverflow = 3,
+                   kSparseWords = 4;
 
 // ---- sketches ---------------------------------------------
 constexpr uint64_t kCmsSeed = 0x5EED5EED5EED5EEDULL;

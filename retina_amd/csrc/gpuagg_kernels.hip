@@ -81,6 +81,40 @@ struct DevSparse {
   uint32_t narrow;
 };
 
+// An update (count c, bytes b) whose segment is full.  Growth mode: appended to the overflow
+// list in the exported entry format, for the host to insert again into a larger table; an
+// entry the list cannot take -- or any, when the table cannot grow (no list) -- is lost
+// and `lost` is added to the dropped counter.  The list's address is read here, from the
+// word the host keeps beside the dropped counter (kSparseWordOverflow, 0: none), not
+// carried as a kernel argument: the aggregation kernels have no scalar register to spare
+// (a pointer in DevSparse cost them spills and c4-remote 0.3 %), and this path is cold.
+// (Inline: as a __noinline__ function the call's register convention cost more than the
+// inlined stores -- wide_kernel 92 -> 100 VGPRs and 5 -> 4 waves a SIMD in the compiler's
+// resource report, against 92 -> 94 inlined.)
+__device__ __forceinline__ void sparse_full(unsigned long long *dropped, uint64_t k0, uint64_t k1, uint64_t k2,
+                                            uint64_t c, uint64_t b, uint64_t lost) {
+  unsigned long long *ovf = (unsigned long long *)dropped[kSparseWordOverflow];
+  if (ovf) {
+    const unsigned long long pos = atomicAdd(&ovf[0], 1ULL);
+    if (pos < ovf[1]) {
+      unsigned long long *e = ovf + kOverflowHeaderWords + pos * kSparseEntryWords;
+      e[0] = k0;
+      e[1] = k1;
+      e[2] = k2;
+      e[3] = c;
+      e[4] = b;
+      return;
+    }
+  }
+  atomicAdd(dropped, (unsigned long long)lost);
+}
+// a compact key in the entry format, as sparse_export_kernel expands it
+__device__ __forceinline__ void sparse_full_compact(unsigned long long *dropped, uint64_t key, uint64_t c) {
+  // (lost: the entry's count -- 1 for every update of a launch; an imported or replayed
+  // entry carries more)
+  sparse_full(dropped, key & 0xFFFFFFFF00000000ULL, 0ULL, key & 0xFFFFFFFFULL, c, 0ULL, c);
+}
+
 // One cached key: tag 0 free, 1 being claimed, 2 published (key words final).
 struct HotKey {
   unsigned long long tag, k0, k1, k2, cnt, byt;
@@ -246,7 +280,7 @@ __device__ __forceinline__ void sparse_add_compact(const DevSparse &s, uint64_t 
       return;
     }
   }
-  atomicAdd(s.dropped, 1ULL);
+  sparse_full_compact(s.dropped, key, c);
 }
 
 // The compact plan's aggregation side: a key goes to its table segment's list (LDS fill
@@ -275,13 +309,20 @@ struct CompactLists {
         return;
       }
     }
-    atomicAdd(dropped, 1ULL);
+    sparse_full_compact(dropped, key, 1ULL);
   }
 };
 
 // Insert-or-add into the sparse table. No lane ever waits for another: a lane that
 // meets a slot whose key is still being published moves on, so a key may occupy
 // more than one slot; the host sums duplicates when it renders series.
+// kWait (the overflow list's replay, where the updates of one key arrive together): such a
+// slot is probed again, at most kImportSpin times, before the lane moves on -- the claimer
+// publishes within a few instructions, so the key keeps one slot.  The lane waits by
+// repeating the probe loop's iteration, not in a loop of its own: a claimer in the same
+// wave publishes in the iteration in which it claimed, whatever the order of the branches.
+constexpr uint32_t kImportSpin = 64;
+template <bool kWait = false>
 __device__ __forceinline__ void sparse_add(const DevSparse &s, uint64_t k0, uint64_t k1,
                                            uint64_t k2, uint64_t c, uint64_t b) {
   if (s.compact) {
@@ -291,6 +332,7 @@ __device__ __forceinline__ void sparse_add(const DevSparse &s, uint64_t k0, uint
   // probing wraps inside the key's segment (the unit sparse_fold_wide_kernel folds)
   const uint32_t h0 = (uint32_t)key_hash(k0, k1, k2) & s.mask, smask = (1u << s.seg_log2) - 1u;
   const uint32_t seg = h0 & ~smask, nprobe = smask < kSparseMaxProbe ? smask + 1u : kSparseMaxProbe;
+  [[maybe_unused]] uint32_t spin = 0;
   for (uint32_t probe = 0; probe < nprobe; ++probe) {
     const uint32_t h = seg | ((h0 + probe) & smask);
     const size_t o = (size_t)h * kSparseSlotWords;  // slot h (k1 = k0 + 1, ...)
@@ -305,6 +347,12 @@ __device__ __forceinline__ void sparse_add(const DevSparse &s, uint64_t k0, uint
     }
     if (cur == k0) {
       const unsigned long long c2 = atomicCAS(&s.k2[o], kKeyPending, kKeyPending);
+      if constexpr (kWait)
+        if (c2 == kKeyPending && spin < kImportSpin) {
+          ++spin;
+          --probe;  // the same slot again
+          continue;
+        }
       if (c2 == k2) {
         const unsigned long long c1 = atomicCAS(&s.k1[o], 0ULL, 0ULL);
         if (c1 == k1) {
@@ -315,7 +363,7 @@ __device__ __forceinline__ void sparse_add(const DevSparse &s, uint64_t k0, uint
       }
     }
   }
-  atomicAdd(s.dropped, c);
+  sparse_full(s.dropped, k0, k1, k2, c, b, c);
 }
 
 // words per segment-list entry: compact key 1, wide 4, narrow wide 3
@@ -1124,6 +1172,28 @@ __global__ __launch_bounds__(1024) void wide_kernel(KArgs a) {
   sp_counts_out(a, sctr);
 }
 
+// Insert-or-add of compact key `key` (count c) into a segment of smask + 1 (key, count)
+// slots held in LDS, h its home slot in the segment: the probe sequence of
+// sparse_add_compact.  Shared by the list fold and the regrow.  false: the segment is full.
+__device__ __forceinline__ bool lds_insert_compact(unsigned long long *seg, uint32_t smask, uint32_t h,
+                                                   unsigned long long key, unsigned long long c) {
+  // (No read of the home slot ahead of the CAS.  The fold used to have one, indexed with
+  // the key's home in the whole table: beyond the segment's LDS for every segment but the
+  // first, where it read zero and fell through -- so it never took effect; taking effect,
+  // with the home masked to the segment, measured C5 +0.5 % per step.  Reading every probe
+  // first, as the wide fold does, measured slower too: a compact probe's CAS is one round
+  // trip already -- profiles/round6/exp/r6r_c5_*)
+  for (uint32_t probe = 0; probe <= smask; ++probe) {
+    const uint32_t i = (h + probe) & smask;
+    const unsigned long long cur = atomicCAS(&seg[2 * i], 0ULL, key);
+    if (cur == 0ULL || cur == key) {
+      atomicAdd(&seg[2 * i + 1], c);
+      return true;
+    }
+  }
+  return false;
+}
+
 // Workgroup w folds table segment w: its 2^seg_log2 (key, count) slots are loaded into
 // LDS, every aggregation workgroup's list of keys for the segment is inserted with LDS
 // 64-bit CAS + add (the probe sequence of sparse_add_compact), and the segment is
@@ -1137,24 +1207,8 @@ __global__ __launch_bounds__(1024) void sparse_fold_kernel(DevSparse s, const un
   fill_lds_u4((uint4 *)seg, (const uint4 *)g, nslot);
   __syncthreads();
   auto insert = [&](unsigned long long key) {
-    const uint32_t h = compact_home(s, key);
-    // the key already in its home slot (a key is published whole by its claiming CAS):
-    // one read, then the no-return add.  (Reading every probe first, as the wide fold does,
-    // measured slower here: a compact probe's CAS is one round trip already --
-    // profiles/round6/exp/r6r_c5_*)
-    if (__hip_atomic_load(&seg[2 * h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == key) {
-      atomicAdd(&seg[2 * h + 1], 1ULL);
-      return;
-    }
-    for (uint32_t probe = 0; probe <= smask; ++probe) {
-      const uint32_t i = (h + probe) & smask;
-      const unsigned long long cur = atomicCAS(&seg[2 * i], 0ULL, key);
-      if (cur == 0ULL || cur == key) {
-        atomicAdd(&seg[2 * i + 1], 1ULL);
-        return;
-      }
-    }
-    atomicAdd(s.dropped, 1ULL);
+    if (!lds_insert_compact(seg, smask, compact_home(s, key) & smask, key, 1ULL))
+      sparse_full_compact(s.dropped, key, 1ULL);
   };
   // lpl lanes per list (a power of two <= 64: the workgroup's lanes spread over the
   // lists), each taking every lpl-th key with 8 loads in flight before its inserts.  A
@@ -1183,6 +1237,65 @@ __global__ __launch_bounds__(1024) void sparse_fold_kernel(DevSparse s, const un
   for (uint32_t i = threadIdx.x; i < nslot; i += blockDim.x) g[i] = ((const ulonglong2 *)seg)[i];
 }
 
+// re-reads of a slot whose key (same k0) is being published before probing on: a claimer
+// publishes within a few instructions, and the bound keeps every insert finite even if
+// the compiler defers the claimer's stores past the loop
+constexpr uint32_t kFoldSpin = 32;
+// A wide-key segment of smask + 1 slots held in LDS, field-major (probes of consecutive slots
+// hit consecutive banks).
+struct LdsWideSeg {
+  unsigned long long *K0, *K1, *K2, *CN, *BY;
+  uint32_t smask;
+};
+// Insert-or-add of key (x0, x1, x2) with count c and bytes b, h its home slot in the segment:
+// the probe sequence and claim / publish protocol of sparse_add on LDS.  Shared by the list
+// fold and the regrow.  false: the segment is full.
+__device__ __forceinline__ bool lds_insert_wide(const LdsWideSeg &t, uint32_t h, uint64_t x0, uint64_t x1,
+                                                uint64_t x2, uint64_t c, uint64_t b) {
+  // Every probe first reads the slot: K2, then K0 and K1, issued together (atomic loads
+  // keep their program order; LDS executes a wave's accesses in order and a claimer
+  // publishes K2 after K1, so a published K2 means the K0 / K1 read after it are final).  A key already in
+  // the segment -- every key once the same flows come back -- costs one LDS round trip
+  // per probe and no-return adds; only a free slot takes the CAS claim.  (The claim CAS
+  // on every probe, then two dependent reads, made each probe three round trips, and a
+  // wave waits for its longest probe run: profiles/round6/exp/r6q_*.)
+  uint32_t spin = 0;
+  for (uint32_t probe = 0; probe <= t.smask;) {
+    const uint32_t i = (h + probe) & t.smask;
+    const unsigned long long p2 = __hip_atomic_load(&t.K2[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    const unsigned long long p0 = __hip_atomic_load(&t.K0[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    const unsigned long long p1 = __hip_atomic_load(&t.K1[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (p2 == x2 && p0 == x0 && p1 == x1) {
+      __hip_atomic_fetch_add(&t.CN[i], (unsigned long long)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if (b) __hip_atomic_fetch_add(&t.BY[i], (unsigned long long)b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      return true;
+    }
+    if (p0 == 0ULL) {
+      const unsigned long long cur = atomicCAS(&t.K0[i], 0ULL, (unsigned long long)x0);
+      if (cur == 0ULL) {
+        t.K1[i] = x1;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __hip_atomic_store(&t.K2[i], (unsigned long long)x2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // publish
+        atomicAdd(&t.CN[i], (unsigned long long)c);
+        if (b) atomicAdd(&t.BY[i], (unsigned long long)b);
+        return true;
+      }
+      // claimed this instant by a lane with the same k0: read the slot again
+      if (cur == x0 && spin < kFoldSpin) {
+        ++spin;
+        continue;
+      }
+    } else if (p0 == x0 && p2 == kKeyPending && spin < kFoldSpin) {
+      // a key with this k0 still being published: wait for it (bounded) rather than
+      // claiming a second slot -- many lanes meeting one new key used to take a slot each
+      ++spin;
+      continue;
+    }
+    ++probe;
+  }
+  return false;
+}
+
 // Workgroup w folds wide-key table segment w (2^seg_log2 slots of k0 k1 k2 cnt byt): the
 // segment is loaded into LDS (field-major, so probes of consecutive slots hit consecutive
 // banks), every aggregation workgroup's list of entries for the segment is inserted with
@@ -1190,10 +1303,6 @@ __global__ __launch_bounds__(1024) void sparse_fold_kernel(DevSparse s, const un
 // (a lane that meets a key still being published moves on, so a key may take two slots;
 // the host sums them) -- and the segment is stored back.  Segments no list reaches are
 // not touched.
-// re-reads of a slot whose key (same k0) is being published before probing on: a claimer
-// publishes within a few instructions, and the bound keeps every insert finite even if
-// the compiler defers the claimer's stores past the loop
-constexpr uint32_t kFoldSpin = 32;
 constexpr uint32_t kFoldSegLoads = 10;  // 16-byte segment loads per lane in flight (5 * 2^12 / 2 / 1024)
 __global__ __launch_bounds__(1024) void sparse_fold_wide_kernel(DevSparse s, const unsigned long long *lists,
                                                                 uint32_t *counts, uint32_t n_lists,
@@ -1256,49 +1365,9 @@ __global__ __launch_bounds__(1024) void sparse_fold_wide_kernel(DevSparse s, con
     }
   }
   __syncthreads();
+  const LdsWideSeg lseg{K0, K1, K2, CN, BY, smask};
   auto insert = [&](uint32_t h, uint64_t x0, uint64_t x1, uint64_t x2, uint64_t c, uint64_t b) {  // h: home slot
-    // Every probe first reads the slot: K2, then K0 and K1, issued together (atomic loads
-    // keep their program order; LDS executes a wave's accesses in order and a claimer
-    // publishes K2 after K1, so a published K2 means the K0 / K1 read after it are final).  A key already in
-    // the segment -- every key once the same flows come back -- costs one LDS round trip
-    // per probe and no-return adds; only a free slot takes the CAS claim.  (The claim CAS
-    // on every probe, then two dependent reads, made each probe three round trips, and a
-    // wave waits for its longest probe run: profiles/round6/exp/r6q_*.)
-    uint32_t spin = 0;
-    for (uint32_t probe = 0; probe < N;) {
-      const uint32_t i = (h + probe) & smask;
-      const unsigned long long p2 = __hip_atomic_load(&K2[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const unsigned long long p0 = __hip_atomic_load(&K0[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      const unsigned long long p1 = __hip_atomic_load(&K1[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (p2 == x2 && p0 == x0 && p1 == x1) {
-        __hip_atomic_fetch_add(&CN[i], (unsigned long long)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (b) __hip_atomic_fetch_add(&BY[i], (unsigned long long)b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        return;
-      }
-      if (p0 == 0ULL) {
-        const unsigned long long cur = atomicCAS(&K0[i], 0ULL, (unsigned long long)x0);
-        if (cur == 0ULL) {
-          K1[i] = x1;
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-          __hip_atomic_store(&K2[i], (unsigned long long)x2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);  // publish
-          atomicAdd(&CN[i], (unsigned long long)c);
-          if (b) atomicAdd(&BY[i], (unsigned long long)b);
-          return;
-        }
-        // claimed this instant by a lane with the same k0: read the slot again
-        if (cur == x0 && spin < kFoldSpin) {
-          ++spin;
-          continue;
-        }
-      } else if (p0 == x0 && p2 == kKeyPending && spin < kFoldSpin) {
-        // a key with this k0 still being published: wait for it (bounded) rather than
-        // claiming a second slot -- many lanes meeting one new key used to take a slot each
-        ++spin;
-        continue;
-      }
-      ++probe;
-    }
-    atomicAdd(s.dropped, (unsigned long long)c);
+    if (!lds_insert_wide(lseg, h, x0, x1, x2, c, b)) sparse_full(s.dropped, x0, x1, x2, c, b, c);
   };
   // (more than 256 lists: lpl lanes per list, each taking every lpl-th entry; a lane loads 4
   // entries before inserting any, so the list reads are in flight together instead of one
@@ -3057,11 +3126,126 @@ __global__ void sparse_export_kernel(DevSparse s, size_t cap_slots, unsigned lon
   }
 }
 
+template <bool kWait>
 __global__ void sparse_import_kernel(DevSparse s, const unsigned long long *in, size_t n) {
   for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n;
        i += (size_t)gridDim.x * blockDim.x) {
     const unsigned long long *e = in + i * kSparseEntryWords;
-    sparse_add(s, e[0], e[1], e[2], e[3], e[4]);
+    sparse_add<kWait>(s, e[0], e[1], e[2], e[3], e[4]);
+  }
+}
+
+// ---- growth of the group-by table (gpuagg_set_sparse_growth) ----------------------------
+// Rebuilds table `old` in the larger, initialised table `neu`.  Workgroup w builds new
+// segment w entirely in LDS (field-major for wide keys, as the list fold holds it) and
+// writes it out once with 16-byte stores: no memory-side atomic, no export buffer.  It
+// streams old segment w & (old segments - 1) -- the whole old table while that is one
+// segment -- hashes every occupied slot for the new size and keeps the keys whose new
+// segment is w: the new segment index extends the old one by high hash bits, so no other
+// old segment holds a key of w.  Equal keys add into one slot, so the duplicate slots a
+// wide table may hold are merged.  Any growth factor; the segment size itself may grow
+// (tables below one full segment).
+// A regrow cannot overflow: new segment w receives keys of one old segment only, which
+// has no more slots than w itself and holds each of them at least once.
+__global__ __launch_bounds__(1024) void sparse_regrow_kernel(DevSparse old, DevSparse neu) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long seg[];
+  const uint32_t w = blockIdx.x, N = 1u << neu.seg_log2, smask = N - 1u;
+  const uint32_t oN = 1u << old.seg_log2, ow = w & (old.mask >> old.seg_log2);
+  if (neu.compact) {
+    ulonglong2 *l2 = (ulonglong2 *)seg;
+    for (uint32_t i = threadIdx.x; i < N; i += blockDim.x) l2[i] = make_ulonglong2(0ULL, 0ULL);
+    __syncthreads();
+    const ulonglong2 *src = (const ulonglong2 *)(old.k0 + 2ull * ((size_t)ow << old.seg_log2));
+    for (uint32_t i0 = threadIdx.x; i0 < oN; i0 += 4 * blockDim.x) {  // 4 slot loads in flight
+      ulonglong2 v[4];
+#pragma unroll
+      for (uint32_t q = 0; q < 4; ++q) {
+        const uint32_t j = i0 + q * blockDim.x;
+        v[q] = j < oN ? src[j] : make_ulonglong2(0ULL, 0ULL);
+      }
+#pragma unroll
+      for (uint32_t q = 0; q < 4; ++q) {
+        if (!v[q].x) continue;
+        const uint32_t h = compact_home(neu, v[q].x);
+        if ((h >> neu.seg_log2) != w) continue;
+        if (!lds_insert_compact(seg, smask, h & smask, v[q].x, v[q].y))
+          sparse_full_compact(neu.dropped, v[q].x, v[q].y);  // (never: see above)
+      }
+    }
+    __syncthreads();
+    ulonglong2 *g = (ulonglong2 *)(neu.k0 + 2ull * ((size_t)w << neu.seg_log2));
+    for (uint32_t i = threadIdx.x; i < N; i += blockDim.x) g[i] = l2[i];
+    return;
+  }
+  unsigned long long *K0 = seg, *K1 = seg + N, *K2 = seg + 2 * N, *CN = seg + 3 * N, *BY = seg + 4 * N;
+  for (uint32_t i = threadIdx.x; i < N; i += blockDim.x) {  // sparse_init_kernel's free slot
+    K0[i] = 0ULL;
+    K1[i] = 0ULL;
+    K2[i] = kKeyPending;
+    CN[i] = 0ULL;
+    BY[i] = 0ULL;
+  }
+  __syncthreads();
+  const LdsWideSeg lseg{K0, K1, K2, CN, BY, smask};
+  auto put = [&](uint64_t x0, uint64_t x1, uint64_t x2, uint64_t c, uint64_t b) {
+    if (!x0) return;
+    const uint32_t h = (uint32_t)key_hash(x0, x1, x2) & neu.mask;
+    if ((h >> neu.seg_log2) != w) return;
+    if (!lds_insert_wide(lseg, h & smask, x0, x1, x2, c, b))
+      sparse_full(neu.dropped, x0, x1, x2, c, b, c);  // (never: see above)
+  };
+  // a lane takes two slots a round: five 16-byte loads (a segment is a whole number of
+  // slot pairs, 16-byte aligned)
+  const ulonglong2 *src =
+      (const ulonglong2 *)(old.k0 + (size_t)kSparseSlotWords * ((size_t)ow << old.seg_log2));
+  for (uint32_t p = threadIdx.x; p < oN / 2; p += blockDim.x) {
+    ulonglong2 v[kSparseSlotWords];
+#pragma unroll
+    for (uint32_t q = 0; q < kSparseSlotWords; ++q) v[q] = src[(size_t)p * kSparseSlotWords + q];
+    put(v[0].x, v[0].y, v[1].x, v[1].y, v[2].x);
+    put(v[2].y, v[3].x, v[3].y, v[4].x, v[4].y);
+  }
+  __syncthreads();
+  const uint32_t nv = kSparseSlotWords * N / 2;
+  auto field = [&](uint32_t word) -> unsigned long long & {
+    const uint32_t slot = word / kSparseSlotWords;
+    return seg[(word - slot * kSparseSlotWords) * N + slot];
+  };
+  ulonglong2 *g = (ulonglong2 *)(neu.k0 + (size_t)kSparseSlotWords * ((size_t)w << neu.seg_log2));
+  for (uint32_t j = threadIdx.x; j < nv; j += blockDim.x) g[j] = make_ulonglong2(field(2 * j), field(2 * j + 1));
+}
+
+// The fallback: every occupied old slot added to the new table with memory-side atomics
+// (tables beyond the segment-list sizes, whose one "segment" is the whole table, and
+// GPUAGG_FLAG_REGROW_DIRECT).
+__global__ void sparse_rehash_direct_kernel(DevSparse old, size_t old_slots, DevSparse neu) {
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < old_slots;
+       i += (size_t)gridDim.x * blockDim.x) {
+    if (old.compact) {
+      const unsigned long long key = old.k0[2 * i];
+      if (key) sparse_add_compact(neu, key, old.k0[2 * i + 1]);
+      continue;
+    }
+    const size_t q = i * kSparseSlotWords;
+    const unsigned long long k0 = old.k0[q];
+    if (k0) sparse_add(neu, k0, old.k1[q], old.k2[q], old.cnt[q], old.byt[q]);
+  }
+}
+
+// The host's growth decision in one readback: the occupied slots added to
+// words[kSparseWordOccupied] (zeroed by the host), the overflow fill (at most the list's
+// capacity) stored beside it.
+__global__ void sparse_count_kernel(DevSparse s, size_t slots, unsigned long long *words) {
+  const size_t stride = s.compact ? 2 : kSparseSlotWords;
+  unsigned long long n = 0;
+  for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < slots; i += (size_t)gridDim.x * blockDim.x)
+    n += s.k0[i * stride] != 0ULL ? 1ULL : 0ULL;
+  n = wave_sum64(n);
+  if ((threadIdx.x & 63u) == 0u && n) atomicAdd(&words[kSparseWordOccupied], n);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const unsigned long long *ovf = (const unsigned long long *)words[kSparseWordOverflow];
+    const unsigned long long fill = ovf ? ovf[0] : 0ULL, cap = ovf ? ovf[1] : 0ULL;
+    words[kSparseWordFill] = fill < cap ? fill : cap;
   }
 }
 
@@ -3490,12 +3674,41 @@ hipError_t launch_sparse_export(const SparseView &v, size_t slots, uint64_t *out
   return hipGetLastError();
 }
 
-hipError_t launch_sparse_import(const SparseView &v, const uint64_t *in, size_t n, hipStream_t st) {
+hipError_t launch_sparse_regrow(const SparseView &old, size_t old_slots, const SparseView &neu, size_t new_slots,
+                                bool direct, hipStream_t st) {
+  if (direct) {
+    hipLaunchKernelGGL(sparse_rehash_direct_kernel, dim3(2048), dim3(256), 0, st, dev_sparse(old), old_slots,
+                       dev_sparse(neu));
+    return hipGetLastError();
+  }
+  // one workgroup per new segment, the segment in dynamic LDS: 16 B a compact slot
+  // (128 KiB at 2^13), 40 B a wide one (160 KiB at 2^12)
+  const size_t seg_lds = (size_t)(neu.compact ? 16 : 8 * kSparseSlotWords) << neu.seg_log2;
+  if (seg_lds > kLdsBytes || (new_slots >> neu.seg_log2) > 0x7FFFFFFFull) return hipErrorInvalidValue;
+  hipError_t e = hipFuncSetAttribute((const void *)sparse_regrow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)kLdsBytes);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(sparse_regrow_kernel, dim3((uint32_t)(new_slots >> neu.seg_log2)), dim3(1024), seg_lds, st,
+                     dev_sparse(old), dev_sparse(neu));
+  return hipGetLastError();
+}
+
+hipError_t launch_sparse_count(const SparseView &v, size_t slots, uint64_t *words, hipStream_t st) {
+  hipLaunchKernelGGL(sparse_count_kernel, dim3(2048), dim3(256), 0, st, dev_sparse(v), slots,
+                     (unsigned long long *)words);
+  return hipGetLastError();
+}
+
+hipError_t launch_sparse_import(const SparseView &v, const uint64_t *in, size_t n, hipStream_t st, bool wait) {
   if (!n) return hipSuccess;
   uint32_t blocks = (uint32_t)((n + 255) / 256);
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(sparse_import_kernel, dim3(blocks), dim3(256), 0, st, dev_sparse(v),
-                     (const unsigned long long *)in, n);
+  if (wait)
+    hipLaunchKernelGGL(sparse_import_kernel<true>, dim3(blocks), dim3(256), 0, st, dev_sparse(v),
+                       (const unsigned long long *)in, n);
+  else
+    hipLaunchKernelGGL(sparse_import_kernel<false>, dim3(blocks), dim3(256), 0, st, dev_sparse(v),
+                       (const unsigned long long *)in, n);
   return hipGetLastError();
 }
 

@@ -25,6 +25,9 @@ struct SparseView {
   uint32_t compact;  // 64-bit keys, 2 words (key, count) per slot at k0
   uint32_t seg_log2; // compact: a key probes only its 2^seg_log2-slot segment
   uint32_t narrow;   // wide keys without port / DNS fields: 24-byte list entries
+  // growth mode: the overflow list (kOverflowHeaderWords) while the table can still grow,
+  // else null; the kernels read it from dropped[kSparseWordOverflow], which the host keeps equal
+  uint64_t *overflow = nullptr;
 };
 
 struct LaunchArgs {
@@ -281,7 +284,17 @@ hipError_t launch_merge_add_u32(uint32_t *dst, const uint32_t *src, size_t n, hi
 hipError_t launch_merge_max_u8(uint8_t *dst, const uint8_t *src, size_t n, hipStream_t st);
 hipError_t launch_sparse_export(const SparseView &v, size_t slots, uint64_t *out, size_t out_cap,
                                 uint64_t *counter, hipStream_t st);
-hipError_t launch_sparse_import(const SparseView &v, const uint64_t *in, size_t n, hipStream_t st);
+// wait: a lane that meets its key still being published reads the slot again (bounded)
+// instead of taking a second slot -- the overflow list's replay
+hipError_t launch_sparse_import(const SparseView &v, const uint64_t *in, size_t n, hipStream_t st,
+                                bool wait = false);
+// Rebuilds table `old` (old_slots slots) in the larger, initialised table `neu`: one LDS-built
+// segment per workgroup (sparse_regrow_kernel), or -- direct -- every old slot added with
+// memory-side atomics (sparse_rehash_direct_kernel).
+hipError_t launch_sparse_regrow(const SparseView &old, size_t old_slots, const SparseView &neu, size_t new_slots,
+                                bool direct, hipStream_t st);
+// words[kSparseWordOccupied] += occupied slots; words[kSparseWordFill] = the overflow fill
+hipError_t launch_sparse_count(const SparseView &v, size_t slots, uint64_t *words, hipStream_t st);
 
 // ---- CPU backend (gpuagg_cpu.cpp): the same launches on host memory and threads --------
 namespace cpu {
@@ -316,6 +329,8 @@ class Engine {
 void sparse_init(const SparseView &v, size_t slots);
 size_t sparse_export(const SparseView &v, size_t slots, uint64_t *out, size_t cap);  // returns entries
 void sparse_import(const SparseView &v, const uint64_t *in, size_t n);
+void sparse_regrow(const SparseView &old, size_t old_slots, const SparseView &neu);  // rehash into neu
+size_t sparse_occupied(const SparseView &v, size_t slots);
 void zero_slots(uint64_t *cnt, uint64_t *byt, uint8_t *hll, uint32_t hll_p, const uint32_t *dead, uint32_t ndead,
                 const Plan &p);
 }  // namespace cpu

@@ -387,6 +387,20 @@ struct gpuagg_ctx {
   uint64_t *d_counter = nullptr;  // export counter
   uint64_t *d_export = nullptr;
   size_t export_cap = 0;
+  // growth mode (gpuagg_set_sparse_growth): the table doubles up to 2^grow_max_log2 slots;
+  // d_overflow is the list full segments append to (sv.overflow points at it while the
+  // table can still grow, else it is null and a full segment loses the update as without
+  // growth)
+  uint32_t grow_max_log2 = 0;  // 0: off
+  uint64_t grow_entries = 0;   // overflow list capacity, entries
+  uint64_t *d_overflow = nullptr;
+  uint64_t sparse_grows = 0, overflow_replayed = 0;
+  const char *regrow_kernel = "";  // what rebuilt the table at the last grow (gpuagg_regrow_kernel_name)
+  // pinned: settle_sparse's readback [kSparseWords], then the overflow fill copied back
+  // behind every launch (ovf_event recorded after it; ovf_armed: a copy is in flight or done)
+  uint64_t *h_grow_words = nullptr;
+  hipEvent_t ovf_event = nullptr;
+  bool ovf_armed = false;
 
   // sketches
   uint32_t *d_cms = nullptr;
@@ -777,6 +791,7 @@ int reset_state(gpuagg_ctx *c) {
   }
   if (c->sparse_slots) {
     HIPCHK(c, x_set_async(c, c->sv.dropped, 0, 8, c->stream));
+    if (c->d_overflow) HIPCHK(c, x_set_async(c, c->d_overflow, 0, 8, c->stream));  // the list is discarded too
     if (c->cpu) cpu::sparse_init(c->sv, c->sparse_slots);
     else {
       ENQ(c);
@@ -789,6 +804,32 @@ int reset_state(gpuagg_ctx *c) {
   return GPUAGG_OK;
 }
 
+// probe / fold segments of a 2^lg-slot table: compact 2^13 slots; wide 2^12 (or the table)
+uint32_t sparse_seg_log2(bool compact, uint32_t lg) {
+  return compact ? std::min<uint32_t>(lg, kSparseSegLog2)
+                 : (lg <= kWideMaxLog2 ? std::min<uint32_t>(lg, kWideSegLog2) : lg);
+}
+
+// Growth mode: allocates the overflow list once the table exists and points the table's
+// view at it while the table can still grow (at 2^grow_max_log2 slots a full segment
+// loses the update, as without growth).
+// The kernels find the list through the word beside the dropped counter
+// (kSparseWordOverflow): nothing may be running on the stream when this is called.
+int ensure_overflow(gpuagg_ctx *c) {
+  if (!c->sparse_slots) return GPUAGG_OK;
+  c->sv.overflow = nullptr;
+  if (c->grow_max_log2 && !c->d_overflow) {
+    if (int rc = dev_alloc(c, &c->d_overflow, kOverflowHeaderWords + c->grow_entries * kSparseEntryWords)) return rc;
+    const uint64_t hdr[kOverflowHeaderWords] = {0, c->grow_entries};
+    HIPCHK(c, x_copy(c, c->d_overflow, hdr, sizeof hdr, hipMemcpyHostToDevice));
+  }
+  if (c->grow_max_log2 && (uint32_t)__builtin_ctzll(c->sparse_slots) < c->grow_max_log2)
+    c->sv.overflow = c->d_overflow;
+  const uint64_t addr = (uint64_t)(uintptr_t)c->sv.overflow;
+  HIPCHK(c, x_copy(c, c->sv.dropped + kSparseWordOverflow, &addr, 8, hipMemcpyHostToDevice));
+  return GPUAGG_OK;
+}
+
 int ensure_sparse(gpuagg_ctx *c) {
   if (c->sparse_slots) return GPUAGG_OK;
   // (the compact layout needs 2 of the 8 words per slot; one allocation serves both)
@@ -797,9 +838,13 @@ int ensure_sparse(gpuagg_ctx *c) {
   const size_t n = (size_t)1 << lg;
   int rc;
   // one interleaved array: slot h = words [5h, 5h + 5) = k0 k1 k2 cnt byt (kSparseSlotWords)
-  if ((rc = dev_alloc(c, &c->sv.k0, n * kSparseSlotWords)) || (rc = dev_alloc(c, &c->sv.dropped, 1)) ||
+  // (sv.dropped: the lost-update counter, then the words settle_sparse reads back with it)
+  if ((rc = dev_alloc(c, &c->sv.k0, n * kSparseSlotWords)) || (rc = dev_alloc(c, &c->sv.dropped, kSparseWords)) ||
       (rc = dev_alloc(c, &c->d_counter, 1)))
     return rc;
+  // (device allocations are not zeroed: no list address before ensure_overflow writes one)
+  const uint64_t zero[kSparseWords] = {};
+  HIPCHK(c, x_copy(c, c->sv.dropped, zero, sizeof zero, hipMemcpyHostToDevice));
   c->sv.k1 = c->sv.k0 + 1;
   c->sv.k2 = c->sv.k0 + 2;
   c->sv.cnt = c->sv.k0 + 3;
@@ -807,7 +852,110 @@ int ensure_sparse(gpuagg_ctx *c) {
   c->sv.mask = (uint32_t)(n - 1);
   c->sv.seg_log2 = std::min<uint32_t>(lg, kSparseSegLog2);
   c->sparse_slots = n;
+  return ensure_overflow(c);
+}
+
+// Rebuilds the group-by table at 2^new_lg slots: the new table is allocated and initialised,
+// the old one regrown into it (launch_sparse_regrow) and freed.  Nothing reads the old
+// view afterwards: the caller has folded the waiting lists.  When the new table cannot be
+// allocated the old one stays as it is.
+int grow_sparse(gpuagg_ctx *c, uint32_t new_lg) {
+  const size_t n = (size_t)1 << new_lg;
+  uint64_t *k0 = nullptr;
+  if (int rc = dev_alloc(c, &k0, n * kSparseSlotWords)) return rc;
+  SparseView nv = c->sv;
+  nv.k0 = k0;
+  nv.k1 = k0 + 1;
+  nv.k2 = k0 + 2;
+  nv.cnt = k0 + 3;
+  nv.byt = k0 + 4;
+  nv.mask = (uint32_t)(n - 1);
+  nv.seg_log2 = sparse_seg_log2(nv.compact != 0, new_lg);
+  // beyond the segment-list sizes a wide table is one "segment": memory-side atomics
+  const bool direct = (c->cfg.flags & GPUAGG_FLAG_REGROW_DIRECT) ||
+                      new_lg > (nv.compact ? kSparseSegLog2 + 12 : kWideMaxLog2);
+  c->regrow_kernel = c->cpu ? "cpu" : direct ? "sparse_rehash_direct_kernel" : "sparse_regrow_kernel";
+  if (c->cpu) {
+    cpu::sparse_init(nv, n);
+    cpu::sparse_regrow(c->sv, c->sparse_slots, nv);
+  } else {
+    ENQ(c);
+    hipError_t e = launch_sparse_init(nv, n, c->stream);
+    if (e == hipSuccess) e = launch_sparse_regrow(c->sv, c->sparse_slots, nv, n, direct, c->stream);
+    if (e == hipSuccess) e = x_sync(c, c->stream);
+    if (e != hipSuccess) {
+      dev_free(c, k0);
+      return fail(c, GPUAGG_EDEVICE, "group-by table regrow to 2^%u: %s", new_lg, hipGetErrorString(e));
+    }
+  }
+  dev_free(c, c->sv.k0);
+  c->sv = nv;
+  c->sparse_slots = n;
+  c->sparse_grows += 1;
+  // (the segment lists, their counters and the export buffer are sized from sparse_slots
+  // where they are used: launch() and the export call sites)
+  return ensure_overflow(c);
+}
+
+// Every reader of the group-by table calls this instead of fold_pending: the waiting lists
+// are folded, then -- growth mode -- one readback of {lost updates, overflow fill, occupied
+// slots} decides whether the table grows: when the overflow list holds entries or the
+// table is more than half full, to the smallest size at which occupied + overflow entries
+// fill at most half of it (so it then sits at 25-50 % load), at most 2^grow_max_log2.  The
+// list is then inserted again; entries that overflow again grow the table once more.
+int settle_sparse(gpuagg_ctx *c) {
+  if (int rc = fold_pending(c)) return rc;
+  if (!c->grow_max_log2 || !c->sparse_slots) return GPUAGG_OK;
+  c->ovf_armed = false;
+  if (!c->h_grow_words) HIPCHK(c, x_host_alloc(c, (void **)&c->h_grow_words, (kSparseWords + 1) * 8));
+  uint64_t *w = c->h_grow_words;
+  for (;;) {  // at most grow_max_log2 - lg rounds
+    const uint32_t lg = (uint32_t)__builtin_ctzll(c->sparse_slots);
+    if (lg >= c->grow_max_log2) break;
+    if (c->cpu) {
+      w[kSparseWordDropped] = *c->sv.dropped;
+      w[kSparseWordFill] = std::min(c->d_overflow[0], c->d_overflow[1]);
+      w[kSparseWordOccupied] = cpu::sparse_occupied(c->sv, c->sparse_slots);
+    } else {
+      HIPCHK(c, x_set_async(c, c->sv.dropped + kSparseWordOccupied, 0, 8, c->stream));
+      HIPCHK(c, launch_sparse_count(c->sv, c->sparse_slots, c->sv.dropped, c->stream));
+      HIPCHK(c, x_copy_async(c, w, c->sv.dropped, kSparseWords * 8, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, x_sync(c, c->stream));
+    }
+    const uint64_t fill = w[kSparseWordFill], occupied = w[kSparseWordOccupied];
+    if (!fill && occupied * 2 <= c->sparse_slots) break;
+    uint32_t new_lg = lg + 1;
+    while (new_lg < c->grow_max_log2 && (occupied + fill) * 2 > ((uint64_t)1 << new_lg)) ++new_lg;
+    if (int rc = grow_sparse(c, new_lg)) return rc;
+    if (!fill) continue;
+    // the list is read from a copy: an entry that overflows again is appended to it
+    uint64_t *tmp = nullptr;
+    if (int rc = dev_alloc(c, &tmp, fill * kSparseEntryWords)) return rc;  // (the list keeps its entries)
+    hipError_t e = x_copy_async(c, tmp, c->d_overflow + kOverflowHeaderWords, fill * kSparseEntryWords * 8,
+                                hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess) e = x_set_async(c, c->d_overflow, 0, 8, c->stream);
+    if (c->cpu) cpu::sparse_import(c->sv, tmp, fill);
+    else if (e == hipSuccess) e = launch_sparse_import(c->sv, tmp, fill, c->stream, true);
+    if (e == hipSuccess) e = x_sync(c, c->stream);
+    dev_free(c, tmp);
+    if (e != hipSuccess) return fail(c, GPUAGG_EDEVICE, "overflow list replay: %s", hipGetErrorString(e));
+    c->overflow_replayed += fill;
+  }
   return GPUAGG_OK;
+}
+
+// The table's entries into the ctx's own export buffer d_export.  The buffer is sized
+// after the settle, which may have grown the table by several doublings.
+int export_table(gpuagg_ctx *c, size_t *n_out) {
+  *n_out = 0;
+  if (int rc = settle_sparse(c)) return rc;
+  if (c->export_cap < c->sparse_slots) {
+    dev_free(c, c->d_export);
+    c->export_cap = 0;
+    if (int rc = dev_alloc(c, &c->d_export, c->sparse_slots * kSparseEntryWords)) return rc;
+    c->export_cap = c->sparse_slots;
+  }
+  return gpuagg_sparse_export(c, c->d_export, c->export_cap, n_out);
 }
 
 // Slots covered by the dense counters / HLL rows for n interned slots: whole 64-slot
@@ -1527,6 +1675,13 @@ int launch(gpuagg_ctx *c, const ColsView &cv, size_t n) {
   if (c->plan.need_ports && !cv.ports) return fail(c, GPUAGG_EINVAL, "enabled metrics read the ports column");
   if ((c->cms_len) && !cv.ports) return fail(c, GPUAGG_EINVAL, "count-min reads the ports column");
   if (c->plan.need_dns && !cv.dns_id) return fail(c, GPUAGG_EINVAL, "enabled DNS metrics read the dns_id column");
+  // growth between syncs: the overflow fill copied back behind the previous launch -- when
+  // that copy is done (no wait when it is not) and the list holds entries, the table grows
+  // before this launch
+  if (c->ovf_armed && hipEventQuery(c->ovf_event) == hipSuccess) {
+    c->ovf_armed = false;
+    if (c->h_grow_words[kSparseWords] && (rc = settle_sparse(c))) return rc;
+  }
   LaunchArgs a{};
   a.ip_slots = c->d_ip;
   a.ip_mask = (uint32_t)(c->ip_cap / 2 - 1);  // bucket mask
@@ -1877,6 +2032,13 @@ int launch(gpuagg_ctx *c, const ColsView &cv, size_t n) {
       c->tm_chain = true;
     }
   }
+  if (c->sv.overflow && c->plan.ngroups > 0) {
+    if (!c->h_grow_words) HIPCHK(c, x_host_alloc(c, (void **)&c->h_grow_words, (kSparseWords + 1) * 8));
+    if (!c->ovf_event) HIPCHK(c, hipEventCreateWithFlags(&c->ovf_event, hipEventDisableTiming));
+    HIPCHK(c, x_copy_async(c, &c->h_grow_words[kSparseWords], c->d_overflow, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipEventRecord(c->ovf_event, c->stream));
+    c->ovf_armed = true;
+  }
   if ((c->cms_len || c->hll_len) && (rc = launch_sketches(c, cv, n))) return rc;
   if (c->lat_enabled && (rc = launch_latency(c, cv, n))) return rc;
   c->stats.records += n;
@@ -2052,6 +2214,9 @@ void gpuagg_destroy(gpuagg_ctx *c) {
   dev_free(c, c->sv.k0);  // k1, k2, cnt, byt point into the same array
   dev_free(c, c->sv.dropped);
   dev_free(c, c->d_counter);
+  dev_free(c, c->d_overflow);
+  x_host_free(c, c->h_grow_words);
+  if (c->ovf_event) hipEventDestroy(c->ovf_event);
   dev_free(c, c->d_export);
   dev_free(c, c->d_cms);
   dev_free(c, c->d_hll);
@@ -2330,8 +2495,7 @@ int gpuagg_reconcile(gpuagg_ctx *c, const gpuagg_metric_options *opts, size_t n)
   c->sv.narrow = (!compact && !p.need_ports && !p.need_dns && (c->cfg.flags & GPUAGG_FLAG_NARROW_ENTRIES)) ? 1u : 0u;
   if (c->sparse_slots) {  // probe / fold segments: compact 2^13 slots; wide 2^12 (or the table)
     const uint32_t lg = (uint32_t)__builtin_ctzll(c->sparse_slots);
-    c->sv.seg_log2 = compact ? std::min<uint32_t>(lg, kSparseSegLog2)
-                             : (lg <= kWideMaxLog2 ? std::min<uint32_t>(lg, kWideSegLog2) : lg);
+    c->sv.seg_log2 = sparse_seg_log2(compact, lg);
   }
   c->inst = inst;
   c->groups = groups;
@@ -2699,7 +2863,7 @@ int gpuagg_retire_slots(gpuagg_ctx *c, size_t *n_retired) {
   if (n_retired) *n_retired = 0;
   int rc = bind(c);
   if (rc) return rc;
-  if ((rc = fold_pending(c))) return rc;
+  if ((rc = settle_sparse(c))) return rc;
   HIPCHK(c, x_sync(c, c->stream));
   std::vector<char> live(c->slots.size(), 0);
   for (const auto &e : c->installed) live[e.second] = 1;
@@ -2733,14 +2897,8 @@ int gpuagg_retire_slots(gpuagg_ctx *c, size_t *n_retired) {
   if (c->sparse_slots) {
     std::vector<char> is_dead(c->slots.size() + 1, 0);  // indexed by slot + 1
     for (uint32_t s : dead) is_dead[s + 1] = 1;
-    if (c->export_cap < c->sparse_slots) {
-      dev_free(c, c->d_export);
-      c->export_cap = 0;
-      if ((rc = dev_alloc(c, &c->d_export, c->sparse_slots * kSparseEntryWords))) return rc;
-      c->export_cap = c->sparse_slots;
-    }
     size_t nent = 0;
-    if ((rc = gpuagg_sparse_export(c, c->d_export, c->export_cap, &nent))) return rc;
+    if ((rc = export_table(c, &nent))) return rc;
     std::vector<uint64_t> ent(nent * kSparseEntryWords);
     if (nent) HIPCHK(c, x_copy(c, ent.data(), c->d_export, ent.size() * 8, hipMemcpyDeviceToHost));
     size_t keep = 0;
@@ -2769,6 +2927,7 @@ int gpuagg_retire_slots(gpuagg_ctx *c, size_t *n_retired) {
       }
       HIPCHK(c, x_copy_async(c, c->sv.dropped, &dropped, 8, hipMemcpyHostToDevice, c->stream));
       HIPCHK(c, x_sync(c, c->stream));
+      if ((rc = settle_sparse(c))) return rc;
     }
   }
   // the dictionary: ids become reusable
@@ -2885,14 +3044,8 @@ int gpuagg_dns_retire(gpuagg_ctx *const *ctxs, size_t n, uint32_t *ids, size_t c
     bool any_dns = false;
     for (const Group &g : c->groups) any_dns |= g.sparse && (g.family == FAM_DNS_REQ || g.family == FAM_DNS_RESP);
     if (!any_dns || !c->sparse_slots) continue;
-    if (c->export_cap < c->sparse_slots) {
-      dev_free(c, c->d_export);
-      c->export_cap = 0;
-      if ((rc = dev_alloc(c, &c->d_export, c->sparse_slots * kSparseEntryWords))) return rc;
-      c->export_cap = c->sparse_slots;
-    }
     size_t nent = 0;
-    if ((rc = gpuagg_sparse_export(c, c->d_export, c->export_cap, &nent))) return rc;
+    if ((rc = export_table(c, &nent))) return rc;
     std::vector<uint64_t> ent(nent * kSparseEntryWords);
     if (nent) HIPCHK(c, x_copy(c, ent.data(), c->d_export, ent.size() * 8, hipMemcpyDeviceToHost));
     for (size_t e = 0; e < nent; ++e) {
@@ -3063,7 +3216,7 @@ int gpuagg_sync(gpuagg_ctx *c) {
   if (!c) return GPUAGG_EINVAL;
   int rc = bind(c);
   if (rc) return rc;
-  if ((rc = fold_pending(c))) return rc;
+  if ((rc = settle_sparse(c))) return rc;
   // the counters come back on the stream, ahead of its one synchronisation (no blocking
   // copy per counter); the timing events are read when the stats are (gpuagg_get_stats)
   if (!c->h_sync_words) HIPCHK(c, x_host_alloc(c, (void **)&c->h_sync_words, 16));
@@ -3782,12 +3935,7 @@ int gpuagg_snapshot(gpuagg_ctx *c, gpuagg_result **out) {
     uint64_t dropped = 0;
     HIPCHK(c, x_copy(c, &dropped, c->sv.dropped, 8, hipMemcpyDeviceToHost));
     c->stats.sparse_dropped = dropped;  // reported with the result (gpuagg_result_dropped)
-    if (c->export_cap < c->sparse_slots) {
-      dev_free(c, c->d_export);
-      if ((rc = dev_alloc(c, &c->d_export, c->sparse_slots * kSparseEntryWords))) return rc;
-      c->export_cap = c->sparse_slots;
-    }
-    rc = gpuagg_sparse_export(c, c->d_export, c->export_cap, &nent);
+    rc = export_table(c, &nent);
     if (rc) return rc;
     ent.resize(nent * kSparseEntryWords);
     if (nent) HIPCHK(c, x_copy(c, ent.data(), c->d_export, ent.size() * 8, hipMemcpyDeviceToHost));
@@ -4394,9 +4542,11 @@ int gpuagg_state(gpuagg_ctx *c, gpuagg_state_desc *o) {
     int rc = bind(c);
     if (rc || (rc = lat_resolve(c))) return rc;
   }
-  if (c->pend.active || c->sk_pend.active) {  // the arrays below are read by the caller: fold what is waiting
+  // the arrays below are read by the caller: fold what is waiting (growth mode: sparse_len
+  // is the size the entries need)
+  if (c->pend.active || c->sk_pend.active || c->grow_max_log2) {
     int rc = bind(c);
-    if (rc || (rc = fold_pending(c))) return rc;
+    if (rc || (rc = settle_sparse(c))) return rc;
     HIPCHK(c, x_sync(c, c->stream));
   }
   o->dense_count = c->d_dense_cnt;
@@ -4421,7 +4571,7 @@ int gpuagg_sparse_export(gpuagg_ctx *c, uint64_t *dev_out, size_t cap, size_t *n
   if (!c->sparse_slots) return GPUAGG_OK;
   int rc = bind(c);
   if (rc) return rc;
-  if ((rc = fold_pending(c))) return rc;
+  if ((rc = settle_sparse(c))) return rc;
   if (c->cpu) {
     const size_t n = cpu::sparse_export(c->sv, c->sparse_slots, dev_out, cap);
     *n_out = std::min(n, cap);
@@ -4446,13 +4596,50 @@ int gpuagg_sparse_import(gpuagg_ctx *c, const uint64_t *dev_in, size_t n) {
   if (!n) return GPUAGG_OK;
   if ((rc = ensure_sparse(c))) return rc;
   if ((rc = fold_pending(c))) return rc;  // (CPU backend: the table has one writer at a time)
-  if (c->cpu) {
-    cpu::sparse_import(c->sv, dev_in, n);
-    return GPUAGG_OK;
+  // growth mode: at most one overflow list of entries between two settles, so an import
+  // of any size into a small table loses nothing
+  const size_t step = c->grow_max_log2 ? (size_t)c->grow_entries : n;
+  for (size_t off = 0; off < n; off += step) {
+    const size_t m = std::min(step, n - off);
+    if (c->cpu) cpu::sparse_import(c->sv, dev_in + off * kSparseEntryWords, m);
+    else {
+      ENQ(c);
+      HIPCHK(c, launch_sparse_import(c->sv, dev_in + off * kSparseEntryWords, m, c->stream));
+      HIPCHK(c, x_sync(c, c->stream));
+    }
+    if ((rc = settle_sparse(c))) return rc;
   }
-  ENQ(c);
-  HIPCHK(c, launch_sparse_import(c->sv, dev_in, n, c->stream));
-  HIPCHK(c, x_sync(c, c->stream));
+  return GPUAGG_OK;
+}
+
+int gpuagg_set_sparse_growth(gpuagg_ctx *c, uint32_t max_log2, uint32_t overflow_entries) {
+  if (!c) return GPUAGG_EINVAL;
+  int rc = bind(c);
+  if (rc) return rc;
+  const uint32_t lg = c->sparse_slots ? (uint32_t)__builtin_ctzll(c->sparse_slots)
+                                      : (c->cfg.sparse_capacity_log2 ? c->cfg.sparse_capacity_log2 : 22);
+  if (max_log2 && (max_log2 < lg || max_log2 > 30))
+    return fail(c, GPUAGG_EINVAL, "sparse growth max_log2 %u out of [%u,30]", max_log2, lg);
+  const uint64_t entries = overflow_entries ? overflow_entries : kOverflowDefaultEntries;
+  // what waits in the current list goes into the table first; the lists of waiting
+  // launches name the list, so they are folded before it may be freed
+  if ((rc = settle_sparse(c))) return rc;
+  HIPCHK(c, x_sync(c, c->stream));  // launches in flight read the list's address
+  if (c->d_overflow && entries != c->grow_entries) dev_free(c, c->d_overflow);
+  c->grow_max_log2 = max_log2;
+  c->grow_entries = entries;
+  return ensure_overflow(c);
+}
+
+const char *gpuagg_regrow_kernel_name(const gpuagg_ctx *c) { return c ? c->regrow_kernel : ""; }
+
+int gpuagg_sparse_info(gpuagg_ctx *c, uint32_t *capacity_log2, uint64_t *grows, uint64_t *overflow_replayed) {
+  if (!c) return GPUAGG_EINVAL;
+  if (capacity_log2)
+    *capacity_log2 = c->sparse_slots ? (uint32_t)__builtin_ctzll(c->sparse_slots)
+                                     : (c->cfg.sparse_capacity_log2 ? c->cfg.sparse_capacity_log2 : 22);
+  if (grows) *grows = c->sparse_grows;
+  if (overflow_replayed) *overflow_replayed = c->overflow_replayed;
   return GPUAGG_OK;
 }
 
@@ -4498,13 +4685,7 @@ int merge_rccl(gpuagg_ctx *const *ctxs, size_t n, const std::vector<int> &devs) 
   for (size_t i = 1; i < n && c0->sparse_slots; ++i) {
     gpuagg_ctx *ci = ctxs[i];
     if ((rc = bind(ci))) return rc;
-    if (ci->export_cap < ci->sparse_slots) {
-      dev_free(ci, ci->d_export);
-      ci->export_cap = 0;
-      if ((rc = dev_alloc(ci, &ci->d_export, ci->sparse_slots * kSparseEntryWords))) return rc;
-      ci->export_cap = ci->sparse_slots;
-    }
-    if ((rc = gpuagg_sparse_export(ci, ci->d_export, ci->export_cap, &m[i]))) return rc;
+    if ((rc = export_table(ci, &m[i]))) return rc;
     total += m[i];
   }
   if ((rc = bind(c0))) return rc;
@@ -4603,7 +4784,8 @@ int gpuagg_merge(gpuagg_ctx *const *ctxs, size_t n) {
   for (size_t i = 0; i < n; ++i) {
     gpuagg_ctx *ci = ctxs[i];
     if ((rc = bind(ci))) return rc;
-    if ((rc = fold_pending(ci))) return rc;
+    // (growth mode: every table takes its size now, before any state is merged)
+    if ((rc = settle_sparse(ci))) return rc;
     if (ci->key_cap < cap && (rc = layout_dense(ci, (uint32_t)cap, true))) return rc;
     HIPCHK(ci, x_sync(ci, ci->stream));
     HIPCHK(ci, x_sync(ci, ci->copy_stream));
@@ -4671,14 +4853,8 @@ int gpuagg_merge(gpuagg_ctx *const *ctxs, size_t n) {
     }
     if (ci->sparse_slots) {  // group-by entries: exported on ci, inserted-and-added on c0
       if ((rc = bind(ci))) break;
-      if (ci->export_cap < ci->sparse_slots) {
-        dev_free(ci, ci->d_export);
-        ci->export_cap = 0;
-        if ((rc = dev_alloc(ci, &ci->d_export, ci->sparse_slots * kSparseEntryWords))) break;
-        ci->export_cap = ci->sparse_slots;
-      }
       size_t m = 0;
-      if ((rc = gpuagg_sparse_export(ci, ci->d_export, ci->export_cap, &m))) break;
+      if ((rc = export_table(ci, &m))) break;
       if ((rc = bind(c0))) break;
       if (m > ent_cap) {
         dev_free(c0, ent);

@@ -86,7 +86,8 @@ class GpuAgg:
     def __init__(self, device: int = 0, remote_context: bool = False, max_slots: int = 1 << 14,
                  max_ips: int = 1 << 16, sparse_capacity_log2: int = 22, cms_depth: int = 0,
                  cms_width_log2: int = 20, hll_precision: int = 0, flags: int = 0,
-                 wide_list_mib: int = 0, latency_limit: int = 0):
+                 wide_list_mib: int = 0, latency_limit: int = 0, sparse_max_log2: int = 0,
+                 sparse_overflow_entries: int = 0):
         self.lib = _abi.load()
         cfg = _abi.Config(_abi.ABI_VERSION, device, 1 if remote_context else 0, max_slots, max_ips,
                           sparse_capacity_log2, cms_depth, cms_width_log2 if cms_depth else 0,
@@ -100,6 +101,13 @@ class GpuAgg:
         self.device = device
         self.remote_context = remote_context
         self._batches: List[HostBatch] = []
+        # growth of the group-by table up to 2^sparse_max_log2 entries (0: fixed size)
+        if sparse_max_log2:
+            try:
+                self._check(self.lib.gpuagg_set_sparse_growth(self.h, sparse_max_log2, sparse_overflow_entries))
+            except GpuAggError:
+                self.close()
+                raise
 
     # -- plumbing --------------------------------------------------------------------
     def _check(self, rc: int) -> None:
@@ -465,6 +473,17 @@ class GpuAgg:
     def sparse_import(self, dev_ptr: int, n: int) -> None:
         self._torch_sync()
         self._check(self.lib.gpuagg_sparse_import(self.h, C.c_void_p(dev_ptr), n))
+
+    def sparse_info(self) -> Dict[str, int]:
+        """The group-by table's current size, its grow operations and the overflow entries
+        inserted again since create (gpuagg_sparse_info)."""
+        lg, grows, replayed = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.gpuagg_sparse_info(self.h, C.byref(lg), C.byref(grows), C.byref(replayed)))
+        return {"capacity_log2": lg.value, "grows": grows.value, "overflow_replayed": replayed.value}
+
+    def regrow_kernel_name(self) -> str:
+        """What rebuilt the group-by table at its last grow ("" before the first one)."""
+        return (self.lib.gpuagg_regrow_kernel_name(self.h) or b"").decode()
 
     def stats(self) -> Dict[str, float]:
         s = _abi.Stats()
