@@ -3,10 +3,12 @@ GPUAGG_FLAG_CPU_BACKEND): a table that starts far too small takes every key thro
 overflow list and the regrow, and the series equal the C port exactly.  The GPU cases are
 in test_gpu_sparse_growth.py."""
 
+import functools
+
 import numpy as np
 import pytest
 
-from .growth_inputs import canonical, slices, snapshot_values, workload
+from .growth_inputs import PARITY, canonical, dns_updates, slices, snapshot_values, workload
 from .helpers import diff_series, make_engine
 
 CPU = 128  # GPUAGG_FLAG_CPU_BACKEND
@@ -147,5 +149,153 @@ def test_setter_arguments():
     g = make_engine(pods, spec, remote, flags=CPU, sparse_capacity_log2=4)
     try:
         assert g.sparse_info() == {"capacity_log2": 4, "grows": 0, "overflow_replayed": 0}
+    finally:
+        g.close()
+
+
+# ---- growth x key layout: the twins of test_gpu_sparse_growth.py, host-fed ----------------
+
+@pytest.mark.parametrize("name", PARITY)
+def test_growth_by_key_layout(name):
+    """Six specs of test_gpu_parity.CASES from a 16-slot table, three host-fed slices: wide
+    keys with port fields and DNS ids, dense groups beside wide keys, compact keys, edge
+    rows."""
+    pods, recs, spec, remote, want = workload(name)
+    g = make_engine(pods, spec, remote, recs=recs, flags=CPU, sparse_capacity_log2=4, sparse_max_log2=22)
+    try:
+        for part in slices(recs, 3):
+            g.submit_numpy(part)
+        got = snapshot_values(g)
+        info = g.sparse_info()
+        assert g.last_dropped == 0 and g.stats()["sparse_dropped"] == 0
+        assert got == want, diff_series(got, want)
+        assert info["grows"] >= 1 and info["overflow_replayed"] > 0, info
+        assert g.regrow_kernel_name() == "cpu"
+    finally:
+        g.close()
+
+
+# ---- conservation while the list overflows -------------------------------------------------
+# (the CPU backend grows the table at a sync only, not between submits: it loses far more
+# than the GPU does on the same input -- what is asserted is that every update is either in
+# the table or counted, not how many)
+
+@functools.lru_cache(maxsize=None)
+def _fixed_table(name, lg):
+    """The reference table of an input, once per process: canonical entries of an engine
+    with a fixed 2^lg-slot table whose series equal the C port's."""
+    pods, recs, spec, remote, want = workload(name)
+    g = make_engine(pods, spec, remote, recs=recs, flags=CPU, sparse_capacity_log2=lg)
+    try:
+        g.submit_numpy(recs)
+        got = snapshot_values(g)
+        assert g.last_dropped == 0 and got == want, diff_series(got, want)
+        return canonical(_export(g))
+    finally:
+        g.close()
+
+
+def _lossy(name, **kw):
+    pods, recs, spec, remote, _ = workload(name)
+    g = make_engine(pods, spec, remote, recs=recs, flags=CPU, **kw)
+    try:
+        for part in slices(recs, 3):
+            g.submit_numpy(part)
+        g.sync()
+        dropped = g.stats()["sparse_dropped"]
+        ent = canonical(_export(g))
+        g.snapshot()
+        assert dropped == g.last_dropped == g.stats()["sparse_dropped"]
+        return ent, dropped
+    finally:
+        g.close()
+
+
+def _check_partial(ent, ref):
+    for key, (c, b) in ent.items():
+        rc, rb = ref[key]  # (KeyError: a key the reference table lacks)
+        assert 0 < c <= rc and b <= rb, (key, c, b, rc, rb)
+
+
+@pytest.mark.parametrize("entries", [256, 0], ids=["256-entry-list", "default-list"])
+def test_wide_conservation_while_list_overflows(entries):
+    ref = _fixed_table("many-wide", 22)
+    ent, dropped = _lossy("many-wide", sparse_capacity_log2=12, sparse_max_log2=22, sparse_overflow_entries=entries)
+    assert sum(c for c, _ in ent.values()) + dropped == 400_000
+    _check_partial(ent, ref)
+    if entries:
+        assert dropped > 0
+    else:
+        assert dropped == 0 and ent == ref
+
+
+def test_compact_conservation_while_list_overflows():
+    want = workload("compact")[4]
+    ref = _fixed_table("compact", 20)
+    ent, dropped = _lossy("compact", sparse_capacity_log2=8, sparse_max_log2=10, sparse_overflow_entries=256)
+    assert dropped > 0
+    assert sum(c for c, _ in ent.values()) + dropped == dns_updates(want) == sum(c for c, _ in ref.values())
+    _check_partial(ent, ref)
+
+
+def test_import_in_steps_of_the_list():
+    """17,421 entries into a 16-slot table with a 256-entry list: 69 steps, nothing lost."""
+    pods, recs, spec, remote, want = workload("small-wide")
+    a = make_engine(pods, spec, remote, recs=recs, flags=CPU, sparse_capacity_log2=20)
+    b = make_engine(pods, spec, remote, recs=recs, flags=CPU, sparse_capacity_log2=4, sparse_max_log2=20,
+                    sparse_overflow_entries=256)
+    try:
+        a.submit_numpy(recs)
+        ent = _export(a)
+        assert -(-len(ent) // 256) == 69
+        b.sparse_import(ent.ctypes.data, len(ent))
+        got = snapshot_values(b)
+        assert b.last_dropped == 0 and b.stats()["sparse_dropped"] == 0
+        assert got == want, diff_series(got, want)
+        assert b.sparse_info()["grows"] >= 1
+    finally:
+        a.close()
+        b.close()
+
+
+# ---- after a grow ------------------------------------------------------------------------
+
+def test_reconcile_layouts_on_a_grown_table():
+    """A wide table grown from 16 slots, then the compact plan on it, then the wide plan
+    again: each plan's records give the C port's series."""
+    pods, recs_w, spec_w, remote, want_w = workload("local-c1-ip-ns-pod-wl")
+    _, recs_c, spec_c, _, want_c = workload("c5-local")
+    g = make_engine(pods, spec_w, remote, recs=recs_c, flags=CPU, sparse_capacity_log2=4, sparse_max_log2=22)
+    try:
+        for spec, recs, want in ((spec_w, recs_w, want_w), (spec_c, recs_c, want_c), (spec_w, recs_w, want_w)):
+            g.reconcile(spec)
+            for part in slices(recs, 3):
+                g.submit_numpy(part)
+            got = snapshot_values(g)
+            assert g.last_dropped == 0
+            assert got == want, diff_series(got, want)
+            assert g.sparse_info()["grows"] >= 1
+    finally:
+        g.close()
+
+
+def test_reset_after_a_grow():
+    """gpuagg_reset empties the grown table and keeps its size: the same records again fit
+    without another trip through the overflow list."""
+    pods, recs, spec, remote, want = workload("local-c1-ip-ns-pod-wl")
+    g = make_engine(pods, spec, remote, recs=recs, flags=CPU, sparse_capacity_log2=4, sparse_max_log2=22)
+    try:
+        g.submit_numpy(recs)
+        assert snapshot_values(g) == want
+        info = g.sparse_info()
+        assert info["grows"] >= 1 and info["overflow_replayed"] > 0
+        g.reset()
+        assert g.snapshot() == {}
+        assert g.sparse_info()["capacity_log2"] == info["capacity_log2"]
+        g.submit_numpy(recs)
+        got = snapshot_values(g)
+        assert g.last_dropped == 0 and g.stats()["sparse_dropped"] == 0
+        assert got == want, diff_series(got, want)
+        assert g.sparse_info()["overflow_replayed"] == info["overflow_replayed"]
     finally:
         g.close()
