@@ -420,6 +420,41 @@ int gpuagg_result_render_text(const gpuagg_result *r, char *buf, size_t cap, siz
 int gpuagg_result_text(const gpuagg_result *r, const char **text, size_t *len);
 void gpuagg_result_free(gpuagg_result *r);
 
+/* Delta snapshots: a second way to read the state, beside gpuagg_snapshot, whose cost
+ * follows what changed and not what is held.
+ *
+ * The series at least one of whose group-by entries or dense bins changed its count or
+ * bytes since this ctx's previous gpuagg_snapshot_delta, each with the INCREMENT since then
+ * as its value (both the count and the bytes object of a view, as in the full snapshot; a
+ * series none of whose entries changed is absent).  *rebased (may be NULL) = 1 means the
+ * increments are relative to zero and the consumer replaces what it has accumulated: the
+ * first call, and the first call after gpuagg_reset, after a gpuagg_reconcile that reset
+ * the state, or on a ctx gpuagg_merge has reset.  Otherwise *rebased = 0 and the consumer
+ * adds them.  Summed per (metric, label tuple) since the last rebased delta (that one
+ * included), the increments equal what gpuagg_snapshot returns at the same point, bit for
+ * bit, for every series it returns -- across table growth, new slots, imports, merges into
+ * ctxs[0] and gpuagg_retire_slots.  (A retired pod's series leave gpuagg_snapshot; their
+ * sums keep the last value handed out, and increments such a pod gathered after the last
+ * delta go with it.)
+ *
+ * The result is an ordinary gpuagg_result: count / series / family / dropped / text / free
+ * work on it.  gpuagg_result_dropped keeps its cumulative meaning.  gpuagg_result_text
+ * renders the increments in the exposition format -- a debugging aid, NOT a /metrics body
+ * -- and the latency families are not part of a delta.
+ *
+ * gpuagg_snapshot neither reads nor moves the baseline.  The baseline (16 bytes per
+ * wide-key table slot or 8 per compact slot, 16 per dense bin, plus 24 per dense bin of
+ * scan output) is allocated at the first call; a ctx that never calls this pays nothing.
+ * If a larger baseline cannot be allocated when the state grows, the call that grew it
+ * returns GPUAGG_ENOMEM after completing its own work, the baseline is dropped and the
+ * next delta is rebased. */
+int gpuagg_snapshot_delta(gpuagg_ctx *ctx, gpuagg_result **out, int *rebased);
+/* Of the last gpuagg_snapshot_delta: table slots and dense bins scanned on the device,
+ * changed table entries and changed dense bins the device emitted (entries carried over a
+ * table rebuild included), and the rebased deltas since create.  Any pointer may be NULL. */
+int gpuagg_delta_info(gpuagg_ctx *ctx, uint64_t *slots_scanned, uint64_t *bins_scanned,
+                      uint64_t *changed_entries, uint64_t *changed_bins, uint64_t *rebases);
+
 /* ------------------------------------------------------------------------------
  * Sketches (new; no reference code): count-min over the 5-tuple and HyperLogLog
  * of distinct destination IPs per source pod.  Estimates read the state of the

@@ -122,6 +122,8 @@ SIGNATURES = [
     ("gpuagg_sync", C.c_int, [C.c_void_p]),
     ("gpuagg_reset", C.c_int, [C.c_void_p]),
     ("gpuagg_snapshot", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    ("gpuagg_snapshot_delta", C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int)]),
+    ("gpuagg_delta_info", C.c_int, [C.c_void_p, u64p, u64p, u64p, u64p, u64p]),
     ("gpuagg_result_count", C.c_size_t, [C.c_void_p]),
     ("gpuagg_result_series", C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p),
                                        C.POINTER(C.c_uint32), C.POINTER(C.POINTER(C.c_char_p)),

@@ -596,6 +596,52 @@ size_t sparse_occupied(const SparseView &v, size_t slots) {
   return n;
 }
 
+size_t sparse_delta(const SparseView &v, size_t slots, uint64_t *shadow, uint64_t *out, size_t cap) {
+  size_t n = 0;
+  for (size_t i = 0; i < slots; ++i) {
+    uint64_t e[kSparseEntryWords] = {};
+    uint64_t *sh = shadow + (v.compact ? i : 2 * i);
+    uint64_t cnt, byt = 0, sb = 0;
+    if (v.compact) {
+      const uint64_t key = v.k0[2 * i];
+      e[0] = key & 0xFFFFFFFF00000000ULL;
+      e[2] = key & 0xFFFFFFFFULL;
+      cnt = v.k0[2 * i + 1];
+    } else {
+      const uint64_t *w = v.k0 + i * kSparseSlotWords;
+      e[0] = w[0], e[1] = w[1], e[2] = w[2];
+      cnt = w[3], byt = w[4];
+      sb = sh[1];
+    }
+    const bool occupied = (v.compact ? (e[0] | e[2]) : e[0]) != 0;
+    if (out && occupied && (cnt != sh[0] || byt != sb)) {
+      e[3] = cnt - sh[0];
+      e[4] = byt - sb;
+      if (n < cap) memcpy(out + n * kSparseEntryWords, e, sizeof e);
+      ++n;
+    }
+    sh[0] = cnt;
+    if (!v.compact) sh[1] = byt;
+  }
+  return n;
+}
+
+size_t dense_delta(const uint64_t *cnt, const uint64_t *byt, uint64_t *sh_cnt, uint64_t *sh_byt, size_t n,
+                   uint64_t *out, size_t cap) {
+  size_t m = 0;
+  for (size_t i = 0; i < n; ++i) {
+    if (cnt[i] == sh_cnt[i] && byt[i] == sh_byt[i]) continue;
+    if (m < cap) {
+      uint64_t *o = out + m * kDenseDeltaWords;
+      o[0] = i, o[1] = cnt[i] - sh_cnt[i], o[2] = byt[i] - sh_byt[i];
+    }
+    ++m;
+    sh_cnt[i] = cnt[i];
+    sh_byt[i] = byt[i];
+  }
+  return m;
+}
+
 void zero_slots(uint64_t *cnt, uint64_t *byt, uint8_t *hll, uint32_t hll_p, const uint32_t *dead, uint32_t ndead,
                 const Plan &p) {
   for (uint32_t k = 0; k < ndead; ++k) {

@@ -380,6 +380,7 @@ GA_HD uint64_t wide_pack12(uint64_t k1, uint64_t k2) { return ((k1 >> 9) << 32) 
 GA_HD uint64_t wide_unpack1(uint64_t n) { return (n >> 32) << 9; }
 GA_HD uint64_t wide_unpack2(uint64_t n) { return (n & 0xFFFFFFFFULL) << 32; }
 constexpr int kSparseEntryWords = 5;  // k0 k1 k2 count bytes
+constexpr int kDenseDeltaWords = 3;   // a changed dense bin of a delta snapshot: bin index, dcount, dbytes
 // Overflow list of the growth mode (gpuagg_set_sparse_growth): one u64 array, word 0 the fill
 // counter (it keeps counting past the capacity), word 1 the capacity in entries, entries
 // of kSparseEntryWords words from word kOverflowHeaderWords on.  An update that finds its

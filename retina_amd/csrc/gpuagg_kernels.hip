@@ -3249,6 +3249,135 @@ __global__ void sparse_count_kernel(DevSparse s, size_t slots, unsigned long lon
   }
 }
 
+// ---- delta snapshots (gpuagg_snapshot_delta) --------------------------------------------
+// Output positions for the wave's lanes with `a`, then its lanes with `b`, behind ONE
+// atomicAdd on *counter (lane 0 adds the wave's total and hands the base out): a scan that
+// finds little changed costs almost no atomics, against one per entry in
+// sparse_export_kernel.  Must be called by the whole wave (all 64 lanes active).
+__device__ __forceinline__ void wave_append2(bool a, bool b, unsigned long long *counter, uint64_t *pos_a,
+                                             uint64_t *pos_b) {
+  const uint64_t ma = __ballot(a), mb = __ballot(b);
+  const uint32_t na = (uint32_t)__popcll(ma), nb = (uint32_t)__popcll(mb);
+  if (na + nb == 0u) return;  // (wave-uniform)
+  const uint32_t ra = __builtin_amdgcn_mbcnt_hi((uint32_t)(ma >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ma, 0u));
+  const uint32_t rb = __builtin_amdgcn_mbcnt_hi((uint32_t)(mb >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mb, 0u));
+  unsigned long long base = 0ULL;
+  if ((threadIdx.x & 63u) == 0u) base = atomicAdd(counter, (unsigned long long)(na + nb));
+  base = readlane64(base, 0u);
+  *pos_a = base + ra;
+  *pos_b = base + na + rb;
+}
+
+// The table against its "published" shadow -- (count, bytes) per wide slot, count per
+// compact slot, zero for a slot never published.  An occupied slot whose counters differ
+// from the shadow is emitted in the export format with the DIFFERENCE as its value
+// (k0 k1 k2 dcount dbytes; a compact key expanded as sparse_export_kernel does) and the
+// shadow takes the current values.  kEmit false: the shadow is set to the table and nothing
+// is emitted (a freshly rebuilt table, whose entries sit in other slots than before).
+// A lane takes two slots a round with 16-byte loads (slot pairs are 16-byte aligned in
+// both layouts, the table has an even number of slots); at most one entry is written per
+// slot, so out_cap >= slots cannot overflow (checked all the same).  Runs alone on the
+// ctx's stream: nothing writes the table meanwhile.
+template <bool kEmit>
+__global__ __launch_bounds__(256) void sparse_delta_kernel(DevSparse s, size_t slots, unsigned long long *shadow,
+                                                           unsigned long long *out, size_t out_cap,
+                                                           unsigned long long *counter) {
+  const size_t npairs = slots / 2, stride = (size_t)gridDim.x * blockDim.x;
+  const size_t rounds = (npairs + stride - 1) / stride;  // the same for every lane: whole waves stay in the loop
+  size_t p = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  for (size_t r = 0; r < rounds; ++r, p += stride) {
+    const bool in = p < npairs;
+    // slots 2p (A) and 2p + 1 (B): key, current counters, shadow
+    uint64_t ka[3] = {0, 0, 0}, kb[3] = {0, 0, 0}, ca = 0, ba = 0, cb = 0, bb = 0;
+    uint64_t sca = 0, sba = 0, scb = 0, sbb = 0;
+    if (in && s.compact) {
+      const ulonglong2 *src = (const ulonglong2 *)s.k0 + 2 * p;
+      const ulonglong2 a = src[0], b = src[1];
+      ka[0] = a.x & 0xFFFFFFFF00000000ULL;
+      ka[2] = a.x & 0xFFFFFFFFULL;
+      ca = a.y;
+      kb[0] = b.x & 0xFFFFFFFF00000000ULL;
+      kb[2] = b.x & 0xFFFFFFFFULL;
+      cb = b.y;
+      if (kEmit) {
+        const ulonglong2 sh = ((const ulonglong2 *)shadow)[p];
+        sca = sh.x;
+        scb = sh.y;
+      }
+    } else if (in) {
+      static_assert(kSparseSlotWords == 5, "k0 k1 k2 cnt byt");
+      const ulonglong2 *src = (const ulonglong2 *)s.k0 + kSparseSlotWords * p;
+      ulonglong2 v[kSparseSlotWords];
+#pragma unroll
+      for (uint32_t q = 0; q < kSparseSlotWords; ++q) v[q] = src[q];
+      ka[0] = v[0].x, ka[1] = v[0].y, ka[2] = v[1].x, ca = v[1].y, ba = v[2].x;
+      kb[0] = v[2].y, kb[1] = v[3].x, kb[2] = v[3].y, cb = v[4].x, bb = v[4].y;
+      if (kEmit) {
+        const ulonglong2 *sh = (const ulonglong2 *)shadow + 2 * p;
+        const ulonglong2 x = sh[0], y = sh[1];
+        sca = x.x, sba = x.y, scb = y.x, sbb = y.y;
+      }
+    }
+    if (!kEmit) {
+      if (in && s.compact) ((ulonglong2 *)shadow)[p] = make_ulonglong2(ca, cb);
+      else if (in) {
+        ulonglong2 *sh = (ulonglong2 *)shadow + 2 * p;
+        sh[0] = make_ulonglong2(ca, ba);
+        sh[1] = make_ulonglong2(cb, bb);
+      }
+      continue;
+    }
+    // (a free slot holds zero counters: its shadow follows without an entry)
+    const bool da = in && (ca != sca || ba != sba), db = in && (cb != scb || bb != sbb);
+    const bool ea = da && (s.compact ? (ka[0] | ka[2]) : ka[0]) != 0ULL;
+    const bool eb = db && (s.compact ? (kb[0] | kb[2]) : kb[0]) != 0ULL;
+    uint64_t pa = 0, pb = 0;
+    wave_append2(ea, eb, counter, &pa, &pb);
+    if (ea && pa < out_cap) {
+      unsigned long long *o = out + pa * kSparseEntryWords;
+      o[0] = ka[0], o[1] = ka[1], o[2] = ka[2], o[3] = ca - sca, o[4] = ba - sba;
+    }
+    if (eb && pb < out_cap) {
+      unsigned long long *o = out + pb * kSparseEntryWords;
+      o[0] = kb[0], o[1] = kb[1], o[2] = kb[2], o[3] = cb - scb, o[4] = bb - sbb;
+    }
+    if (da || db) {
+      if (s.compact) ((ulonglong2 *)shadow)[p] = make_ulonglong2(ca, cb);
+      else {
+        ulonglong2 *sh = (ulonglong2 *)shadow + 2 * p;
+        if (da) sh[0] = make_ulonglong2(ca, ba);
+        if (db) sh[1] = make_ulonglong2(cb, bb);
+      }
+    }
+  }
+}
+
+// The same over the dense bins: a bin whose count or bytes differ from the shadow arrays
+// is emitted as (bin index, dcount, dbytes) -- kDenseDeltaWords -- and the shadow updated.
+__global__ __launch_bounds__(256) void dense_delta_kernel(const unsigned long long *cnt, const unsigned long long *byt,
+                                                          unsigned long long *sh_cnt, unsigned long long *sh_byt,
+                                                          size_t n, unsigned long long *out, size_t out_cap,
+                                                          unsigned long long *counter) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const size_t rounds = (n + stride - 1) / stride;  // the same for every lane
+  size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+  for (size_t r = 0; r < rounds; ++r, i += stride) {
+    const bool in = i < n;
+    const uint64_t c = in ? cnt[i] : 0ULL, b = in ? byt[i] : 0ULL;
+    const uint64_t sc = in ? sh_cnt[i] : 0ULL, sb = in ? sh_byt[i] : 0ULL;
+    const bool d = in && (c != sc || b != sb);
+    uint64_t pos = 0, unused = 0;
+    wave_append2(d, false, counter, &pos, &unused);
+    if (!d) continue;
+    if (pos < out_cap) {
+      unsigned long long *o = out + pos * kDenseDeltaWords;
+      o[0] = i, o[1] = c - sc, o[2] = b - sb;
+    }
+    sh_cnt[i] = c;
+    sh_byt[i] = b;
+  }
+}
+
 // ---- slot retirement and the single-process multi-GPU merge ----------------------------
 // Zeroes the dense bins of retired slots: workgroup b takes dead slot b, its lanes the
 // (group, side, sub) bins of that slot in every endpoint-keyed dense group.
@@ -3696,6 +3825,32 @@ hipError_t launch_sparse_regrow(const SparseView &old, size_t old_slots, const S
 hipError_t launch_sparse_count(const SparseView &v, size_t slots, uint64_t *words, hipStream_t st) {
   hipLaunchKernelGGL(sparse_count_kernel, dim3(2048), dim3(256), 0, st, dev_sparse(v), slots,
                      (unsigned long long *)words);
+  return hipGetLastError();
+}
+
+hipError_t launch_sparse_delta(const SparseView &v, size_t slots, uint64_t *shadow, uint64_t *out, size_t out_cap,
+                               uint64_t *counter, hipStream_t st) {
+  if (slots < 2 || (slots & 1)) return slots ? hipErrorInvalidValue : hipSuccess;  // (tables are 2^k >= 16 slots)
+  const size_t need = (slots / 2 + 255) / 256;
+  const dim3 grid((uint32_t)(need < 2048 ? need : 2048));
+  if (out)
+    hipLaunchKernelGGL(sparse_delta_kernel<true>, grid, dim3(256), 0, st, dev_sparse(v), slots,
+                       (unsigned long long *)shadow, (unsigned long long *)out, out_cap, (unsigned long long *)counter);
+  else
+    hipLaunchKernelGGL(sparse_delta_kernel<false>, grid, dim3(256), 0, st, dev_sparse(v), slots,
+                       (unsigned long long *)shadow, (unsigned long long *)nullptr, (size_t)0,
+                       (unsigned long long *)nullptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_dense_delta(const uint64_t *cnt, const uint64_t *byt, uint64_t *sh_cnt, uint64_t *sh_byt, size_t n,
+                              uint64_t *out, size_t out_cap, uint64_t *counter, hipStream_t st) {
+  if (!n) return hipSuccess;
+  const size_t need = (n + 255) / 256;
+  hipLaunchKernelGGL(dense_delta_kernel, dim3((uint32_t)(need < 2048 ? need : 2048)), dim3(256), 0, st,
+                     (const unsigned long long *)cnt, (const unsigned long long *)byt, (unsigned long long *)sh_cnt,
+                     (unsigned long long *)sh_byt, n, (unsigned long long *)out, out_cap,
+                     (unsigned long long *)counter);
   return hipGetLastError();
 }
 

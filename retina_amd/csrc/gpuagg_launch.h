@@ -295,6 +295,15 @@ hipError_t launch_sparse_regrow(const SparseView &old, size_t old_slots, const S
                                 bool direct, hipStream_t st);
 // words[kSparseWordOccupied] += occupied slots; words[kSparseWordFill] = the overflow fill
 hipError_t launch_sparse_count(const SparseView &v, size_t slots, uint64_t *words, hipStream_t st);
+// Delta snapshots: the occupied slots whose (count, bytes) differ from `shadow` (2 words a
+// wide slot, 1 a compact slot) appended to out (kSparseEntryWords each, the differences as
+// values; out_cap >= slots entries) behind *counter, and the shadow set to the table.
+// out null: the shadow is set to the table and nothing is emitted (rebase).
+hipError_t launch_sparse_delta(const SparseView &v, size_t slots, uint64_t *shadow, uint64_t *out, size_t out_cap,
+                               uint64_t *counter, hipStream_t st);
+// The same over n dense bins and their shadow arrays: kDenseDeltaWords per changed bin.
+hipError_t launch_dense_delta(const uint64_t *cnt, const uint64_t *byt, uint64_t *sh_cnt, uint64_t *sh_byt, size_t n,
+                              uint64_t *out, size_t out_cap, uint64_t *counter, hipStream_t st);
 
 // ---- CPU backend (gpuagg_cpu.cpp): the same launches on host memory and threads --------
 namespace cpu {
@@ -331,6 +340,10 @@ size_t sparse_export(const SparseView &v, size_t slots, uint64_t *out, size_t ca
 void sparse_import(const SparseView &v, const uint64_t *in, size_t n);
 void sparse_regrow(const SparseView &old, size_t old_slots, const SparseView &neu);  // rehash into neu
 size_t sparse_occupied(const SparseView &v, size_t slots);
+// launch_sparse_delta / launch_dense_delta as host loops; they return the entries emitted
+size_t sparse_delta(const SparseView &v, size_t slots, uint64_t *shadow, uint64_t *out, size_t cap);
+size_t dense_delta(const uint64_t *cnt, const uint64_t *byt, uint64_t *sh_cnt, uint64_t *sh_byt, size_t n,
+                   uint64_t *out, size_t cap);
 void zero_slots(uint64_t *cnt, uint64_t *byt, uint8_t *hll, uint32_t hll_p, const uint32_t *dead, uint32_t ndead,
                 const Plan &p);
 }  // namespace cpu

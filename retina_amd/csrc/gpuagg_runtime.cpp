@@ -402,6 +402,26 @@ struct gpuagg_ctx {
   hipEvent_t ovf_event = nullptr;
   bool ovf_armed = false;
 
+  // delta snapshots (gpuagg_snapshot_delta): the "published" shadow of the state -- what
+  // the deltas handed out so far add up to, position for position -- allocated at the first
+  // delta (zero: that delta is the whole state, "rebased") and freed by whatever clears the
+  // state (delta_drop: the next delta is rebased again).  Nothing else allocates or runs
+  // delta code, so a ctx that never asks for a delta pays nothing.
+  struct Delta {
+    bool active = false;
+    uint64_t *d_sparse = nullptr;  // per table slot: (count, bytes) wide, count compact
+    size_t slots = 0;
+    uint64_t *d_cnt = nullptr, *d_byt = nullptr;  // per dense bin
+    size_t bins = 0;
+    uint64_t *d_bins_out = nullptr;  // dense_delta's output, kDenseDeltaWords per bin
+    size_t bins_out_cap = 0;
+    uint64_t *d_ctr = nullptr;  // the scans' append counter (device mode)
+    // changed entries scanned off a table about to be rebuilt (growth, retire): the shadow is
+    // positional, so they wait here for the next delta and the new table's shadow is rebased
+    std::vector<uint64_t> carry;
+    uint64_t slots_scanned = 0, bins_scanned = 0, changed_entries = 0, changed_bins = 0, rebases = 0;
+  } delta;
+
   // sketches
   uint32_t *d_cms = nullptr;
   size_t cms_len = 0;
@@ -783,8 +803,11 @@ void drop_pending(gpuagg_ctx *c) {
   if (c->cpu) c->cpu->drop();
 }
 
+void delta_drop(gpuagg_ctx *c);
+
 int reset_state(gpuagg_ctx *c) {
   drop_pending(c);
+  delta_drop(c);  // the next delta starts from zero again ("rebased")
   if (c->dense_len) {
     HIPCHK(c, x_set_async(c, c->d_dense_cnt, 0, c->dense_len * 8, c->stream));
     HIPCHK(c, x_set_async(c, c->d_dense_byt, 0, c->dense_len * 8, c->stream));
@@ -855,6 +878,96 @@ int ensure_sparse(gpuagg_ctx *c) {
   return ensure_overflow(c);
 }
 
+// The ctx's own export buffer d_export, one entry per slot of the current table.
+int ensure_export(gpuagg_ctx *c) {
+  if (c->export_cap >= c->sparse_slots) return GPUAGG_OK;
+  dev_free(c, c->d_export);
+  c->export_cap = 0;
+  if (int rc = dev_alloc(c, &c->d_export, c->sparse_slots * kSparseEntryWords)) return rc;
+  c->export_cap = c->sparse_slots;
+  return GPUAGG_OK;
+}
+
+// ---- delta snapshots: the shadow and what keeps it true -----------------------------------
+// Frees the baseline: the next gpuagg_snapshot_delta starts from zero and says "rebased".
+void delta_drop(gpuagg_ctx *c) {
+  gpuagg_ctx::Delta &d = c->delta;
+  if (!d.active) return;
+  (void)x_sync(c, c->stream);
+  dev_free(c, d.d_sparse);
+  dev_free(c, d.d_cnt);
+  dev_free(c, d.d_byt);
+  dev_free(c, d.d_bins_out);
+  dev_free(c, d.d_ctr);
+  d.slots = d.bins = d.bins_out_cap = 0;
+  std::vector<uint64_t>().swap(d.carry);
+  d.active = false;
+}
+
+// The table's changed entries (differences as values) appended to dst, the shadow set to
+// the table.  The stream is idle and the lists folded (the caller settled the table).
+int delta_scan_sparse(gpuagg_ctx *c, std::vector<uint64_t> &dst, uint64_t *n_out) {
+  gpuagg_ctx::Delta &d = c->delta;
+  *n_out = 0;
+  if (!c->sparse_slots) return GPUAGG_OK;
+  if (int rc = ensure_export(c)) return rc;
+  uint64_t n = 0;
+  if (c->cpu) {
+    n = cpu::sparse_delta(c->sv, c->sparse_slots, d.d_sparse, c->d_export, c->export_cap);
+  } else {
+    HIPCHK(c, x_set_async(c, d.d_ctr, 0, 8, c->stream));
+    ENQ(c);
+    HIPCHK(c, launch_sparse_delta(c->sv, c->sparse_slots, d.d_sparse, c->d_export, c->export_cap, d.d_ctr, c->stream));
+    HIPCHK(c, x_copy_async(c, &n, d.d_ctr, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, x_sync(c, c->stream));
+  }
+  if (n > c->export_cap) return fail(c, GPUAGG_ESTATE, "delta scan emitted %llu entries from %zu slots",
+                                     (unsigned long long)n, c->sparse_slots);
+  if (n) {
+    const size_t o = dst.size();
+    dst.resize(o + n * kSparseEntryWords);
+    HIPCHK(c, x_copy(c, dst.data() + o, c->d_export, n * kSparseEntryWords * 8, hipMemcpyDeviceToHost));
+  }
+  *n_out = n;
+  return GPUAGG_OK;
+}
+
+// Before the table is rebuilt (its entries move to other slots): what changed since the
+// last delta goes to the carry list.  The caller then rebuilds and calls delta_rebase.
+// On failure the baseline is dropped (the next delta is rebased) and the code returned.
+int delta_carry(gpuagg_ctx *c) {
+  gpuagg_ctx::Delta &d = c->delta;
+  if (!d.active || !d.d_sparse) return GPUAGG_OK;
+  uint64_t n = 0;
+  int rc = d.slots == c->sparse_slots ? delta_scan_sparse(c, d.carry, &n) : GPUAGG_ESTATE;
+  if (rc) delta_drop(c);
+  return rc;
+}
+
+// After the rebuild: a shadow of the table's size, set to the table's counters.
+int delta_rebase(gpuagg_ctx *c) {
+  gpuagg_ctx::Delta &d = c->delta;
+  if (!d.active || !d.d_sparse) return GPUAGG_OK;
+  int rc = GPUAGG_OK;
+  if (d.slots != c->sparse_slots) {
+    dev_free(c, d.d_sparse);
+    d.slots = 0;
+    if ((rc = dev_alloc(c, &d.d_sparse, c->sparse_slots * (c->sv.compact ? 1 : 2))) == GPUAGG_OK)
+      d.slots = c->sparse_slots;
+  }
+  if (rc == GPUAGG_OK) {
+    if (c->cpu) cpu::sparse_delta(c->sv, c->sparse_slots, d.d_sparse, nullptr, 0);
+    else {
+      ENQ(c);
+      hipError_t e = launch_sparse_delta(c->sv, c->sparse_slots, d.d_sparse, nullptr, 0, nullptr, c->stream);
+      if (e == hipSuccess) e = x_sync(c, c->stream);
+      if (e != hipSuccess) rc = fail(c, GPUAGG_EDEVICE, "delta rebase: %s", hipGetErrorString(e));
+    }
+  }
+  if (rc) delta_drop(c);
+  return rc;
+}
+
 // Rebuilds the group-by table at 2^new_lg slots: the new table is allocated and initialised,
 // the old one regrown into it (launch_sparse_regrow) and freed.  Nothing reads the old
 // view afterwards: the caller has folded the waiting lists.  When the new table cannot be
@@ -874,6 +987,9 @@ int grow_sparse(gpuagg_ctx *c, uint32_t new_lg) {
   // beyond the segment-list sizes a wide table is one "segment": memory-side atomics
   const bool direct = (c->cfg.flags & GPUAGG_FLAG_REGROW_DIRECT) ||
                       new_lg > (nv.compact ? kSparseSegLog2 + 12 : kWideMaxLog2);
+  // (a delta baseline: the old table's changes are carried, the new table's shadow rebased;
+  // a failure there drops the baseline and is reported once the table has grown)
+  const int drc = delta_carry(c);
   c->regrow_kernel = c->cpu ? "cpu" : direct ? "sparse_rehash_direct_kernel" : "sparse_regrow_kernel";
   if (c->cpu) {
     cpu::sparse_init(nv, n);
@@ -894,7 +1010,8 @@ int grow_sparse(gpuagg_ctx *c, uint32_t new_lg) {
   c->sparse_grows += 1;
   // (the segment lists, their counters and the export buffer are sized from sparse_slots
   // where they are used: launch() and the export call sites)
-  return ensure_overflow(c);
+  if (int rc = ensure_overflow(c)) return rc;
+  return drc ? drc : delta_rebase(c);
 }
 
 // Every reader of the group-by table calls this instead of fold_pending: the waiting lists
@@ -949,12 +1066,7 @@ int settle_sparse(gpuagg_ctx *c) {
 int export_table(gpuagg_ctx *c, size_t *n_out) {
   *n_out = 0;
   if (int rc = settle_sparse(c)) return rc;
-  if (c->export_cap < c->sparse_slots) {
-    dev_free(c, c->d_export);
-    c->export_cap = 0;
-    if (int rc = dev_alloc(c, &c->d_export, c->sparse_slots * kSparseEntryWords)) return rc;
-    c->export_cap = c->sparse_slots;
-  }
+  if (int rc = ensure_export(c)) return rc;
   return gpuagg_sparse_export(c, c->d_export, c->export_cap, n_out);
 }
 
@@ -975,6 +1087,7 @@ int layout_dense(gpuagg_ctx *c, uint32_t key_cap, bool keep) {
     if (int rc = fold_pending(c)) return rc;
   } else {
     drop_pending(c);
+    delta_drop(c);  // the state is cleared: the next delta is rebased
   }
   uint64_t total = 0;
   std::vector<uint64_t> base(c->groups.size(), 0), old_base(c->groups.size(), 0), old_nbins(c->groups.size(), 0);
@@ -1021,6 +1134,41 @@ int layout_dense(gpuagg_ctx *c, uint32_t key_cap, bool keep) {
     c->d_hll = hll;
     c->hll_len = len;
   }
+  // a delta baseline's shadow arrays move exactly as the counters do; if the larger ones
+  // cannot be had the baseline is dropped and the call reports it once the layout is done
+  int drc = GPUAGG_OK;
+  gpuagg_ctx::Delta &dl = c->delta;
+  if (dl.active && dl.d_cnt) {
+    uint64_t *scnt = nullptr, *sbyt = nullptr;
+    if ((drc = dev_alloc(c, &scnt, total)) || (drc = dev_alloc(c, &sbyt, total))) {
+      dev_free(c, scnt);
+      delta_drop(c);
+    } else {
+      hipError_t e = hipSuccess;
+      if (total && (e = x_set_async(c, scnt, 0, total * 8, c->stream)) == hipSuccess)
+        e = x_set_async(c, sbyt, 0, total * 8, c->stream);
+      for (size_t g = 0; e == hipSuccess && dl.bins && g < c->groups.size(); ++g) {
+        if (c->groups[g].sparse || !old_nbins[g]) continue;
+        const uint64_t nb = std::min<uint64_t>(old_nbins[g], total - base[g]);
+        e = x_copy_async(c, scnt + base[g], dl.d_cnt + old_base[g], nb * 8, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess)
+          e = x_copy_async(c, sbyt + base[g], dl.d_byt + old_base[g], nb * 8, hipMemcpyDeviceToDevice, c->stream);
+      }
+      if (e == hipSuccess) e = x_sync(c, c->stream);
+      if (e != hipSuccess) {
+        dev_free(c, scnt);
+        dev_free(c, sbyt);
+        delta_drop(c);
+        drc = fail(c, GPUAGG_EDEVICE, "delta shadow re-layout: %s", hipGetErrorString(e));
+      } else {
+        dev_free(c, dl.d_cnt);
+        dev_free(c, dl.d_byt);
+        dl.d_cnt = scnt;
+        dl.d_byt = sbyt;
+        dl.bins = total;
+      }
+    }
+  }
   HIPCHK(c, x_sync(c, c->stream));
   dev_free(c, c->d_dense_cnt);
   dev_free(c, c->d_dense_byt);
@@ -1036,7 +1184,7 @@ int layout_dense(gpuagg_ctx *c, uint32_t key_cap, bool keep) {
     c->plan.g[g].nbins = (uint32_t)(gr.nkeys * 2 * gr.nsub);
   }
   c->key_cap = key_cap;
-  return GPUAGG_OK;
+  return drc;
 }
 
 void drain_timing(gpuagg_ctx *c) {
@@ -2218,6 +2366,7 @@ void gpuagg_destroy(gpuagg_ctx *c) {
   x_host_free(c, c->h_grow_words);
   if (c->ovf_event) hipEventDestroy(c->ovf_event);
   dev_free(c, c->d_export);
+  delta_drop(c);
   dev_free(c, c->d_cms);
   dev_free(c, c->d_hll);
   dev_free(c, c->d_spill);
@@ -2888,12 +3037,20 @@ int gpuagg_retire_slots(gpuagg_ctx *c, size_t *n_retired) {
       e = launch_zero_slots(c->dense_len ? c->d_dense_cnt : nullptr, c->d_dense_byt, c->hll_len ? c->d_hll : nullptr,
                             c->cfg.hll_precision, d, (uint32_t)dead_dev.size(), c->plan, c->stream);
     }
+    // a delta baseline: the same bins of the shadow, so a reused slot starts from zero in
+    // both (the sum of the deltas keeps a retired pod's last published value)
+    if (e == hipSuccess && c->delta.active && c->delta.d_cnt && c->delta.bins == c->dense_len) {
+      if (c->cpu) cpu::zero_slots(c->delta.d_cnt, c->delta.d_byt, nullptr, 0, d, (uint32_t)dead_dev.size(), c->plan);
+      else e = launch_zero_slots(c->delta.d_cnt, c->delta.d_byt, nullptr, 0, d, (uint32_t)dead_dev.size(), c->plan,
+                                 c->stream);
+    }
     if (e == hipSuccess) e = x_sync(c, c->stream);
     dev_free(c, d);
     if (e != hipSuccess) return fail(c, GPUAGG_EDEVICE, "retire: %s", hipGetErrorString(e));
   }
   // group-by entries keyed by a dead slot (as source or destination): the table is
   // rebuilt without them (export, filter on the host, re-insert)
+  int drc = GPUAGG_OK;  // a delta baseline that had to be dropped: reported once the slots are retired
   if (c->sparse_slots) {
     std::vector<char> is_dead(c->slots.size() + 1, 0);  // indexed by slot + 1
     for (uint32_t s : dead) is_dead[s + 1] = 1;
@@ -2908,6 +3065,22 @@ int gpuagg_retire_slots(gpuagg_ctx *c, size_t *n_retired) {
       if ((s1 < is_dead.size() && is_dead[s1]) || (d1 < is_dead.size() && is_dead[d1])) continue;
       memmove(&ent[keep * kSparseEntryWords], w, kSparseEntryWords * 8);
       ++keep;
+    }
+    // a delta baseline: carried entries keyed by a dead slot go the same way (their labels
+    // are about to be wiped); the rebuild below moves the others, so their changes are
+    // carried first and the shadow rebased afterwards
+    if (c->delta.active) {
+      if (keep != nent) drc = delta_carry(c);
+      std::vector<uint64_t> &cy = c->delta.carry;
+      size_t ck = 0;
+      for (size_t i = 0; i < cy.size() / kSparseEntryWords; ++i) {
+        const uint64_t *w = &cy[i * kSparseEntryWords];
+        const uint32_t s1 = key_s_slot1(w[0]), d1 = key_d_slot1(w[1]);
+        if ((s1 < is_dead.size() && is_dead[s1]) || (d1 < is_dead.size() && is_dead[d1])) continue;
+        memmove(&cy[ck * kSparseEntryWords], w, kSparseEntryWords * 8);
+        ++ck;
+      }
+      cy.resize(ck * kSparseEntryWords);
     }
     if (keep != nent) {
       uint64_t dropped = 0;
@@ -2927,6 +3100,7 @@ int gpuagg_retire_slots(gpuagg_ctx *c, size_t *n_retired) {
       }
       HIPCHK(c, x_copy_async(c, c->sv.dropped, &dropped, 8, hipMemcpyHostToDevice, c->stream));
       HIPCHK(c, x_sync(c, c->stream));
+      if (!drc) drc = delta_rebase(c);
       if ((rc = settle_sparse(c))) return rc;
     }
   }
@@ -2941,7 +3115,7 @@ int gpuagg_retire_slots(gpuagg_ctx *c, size_t *n_retired) {
   ++c->slots_version;
   std::sort(c->free_slots.begin(), c->free_slots.end(), std::greater<int32_t>());  // lowest id first
   if (n_retired) *n_retired = dead.size();
-  return GPUAGG_OK;
+  return drc;
 }
 
 static std::string dns_key(uint32_t rcode, const std::string &qtypes, const std::string &query,
@@ -3541,8 +3715,10 @@ void ctx_values_fast(uint8_t opts, uint32_t ip, const SlotCanon &sc, uint32_t ci
   if (opts & OPT_PORT) append_port(out, port17);
 }
 
+// delta: dc / db / ent hold increments (gpuagg_snapshot_delta: the changed bins scattered
+// into zeroed arrays, the changed entries) -- a bin then counts when either word is set.
 int render_series(gpuagg_ctx *c, const std::vector<uint64_t> &dc, const std::vector<uint64_t> &db,
-                  const std::vector<uint64_t> &ent, size_t nent, gpuagg_result *r) {
+                  const std::vector<uint64_t> &ent, size_t nent, gpuagg_result *r, bool delta = false) {
   const bool local = !c->remote;
   const size_t ns_len = strlen("networkobservability_");
   r->fam.resize(c->inst.size());
@@ -3768,7 +3944,7 @@ int render_series(gpuagg_ctx *c, const std::vector<uint64_t> &dc, const std::vec
         for (uint32_t side = 0; side < 2; ++side)
           for (uint32_t sub = 0; sub < g.nsub; ++sub) {
             const uint64_t idx = g.dense_base + (key * 2 + side) * g.nsub + sub;
-            if (!dc[idx]) continue;  // (a bytes series exists whenever its count does)
+            if (!dc[idx] && !(delta && db[idx])) continue;  // (a bytes series exists whenever its count does)
             const uint32_t pre = g.family == FAM_DROP ? (sub << 4) | side : g.family == FAM_TCPFLAGS ? sub : side;
             for (uint32_t vi : group_views[gi]) {
               LKey k{};
@@ -3963,6 +4139,108 @@ int gpuagg_snapshot(gpuagg_ctx *c, gpuagg_result **out) {
     render_latency(ls, r->extra_text);
   }
   *out = r;
+  return GPUAGG_OK;
+}
+
+int gpuagg_snapshot_delta(gpuagg_ctx *c, gpuagg_result **out, int *rebased) {
+  if (!c || !out) return GPUAGG_EINVAL;
+  *out = nullptr;
+  if (rebased) *rebased = 0;
+  int rc = gpuagg_sync(c);  // (a table that grows here carries its changes: grow_sparse)
+  if (rc) return rc;
+  gpuagg_ctx::Delta &d = c->delta;
+  // (the moves of the state keep the shadow's sizes; one that did not starts over)
+  if (d.active && ((d.slots && d.slots != c->sparse_slots) || (d.bins && d.bins != c->dense_len))) delta_drop(c);
+  const bool fresh = !d.active;
+  d.active = true;
+  // shadows of state that has none yet, zeroed: its first delta is all of it
+  auto zeroed = [&](uint64_t **p, size_t words) -> int {
+    if (int e = dev_alloc(c, p, words)) return e;
+    HIPCHK(c, x_set_async(c, *p, 0, words * 8, c->stream));
+    return GPUAGG_OK;
+  };
+  if (!c->cpu && !d.d_ctr) rc = zeroed(&d.d_ctr, 1);
+  if (!rc && c->sparse_slots && !d.d_sparse &&
+      !(rc = zeroed(&d.d_sparse, c->sparse_slots * (c->sv.compact ? 1 : 2))))
+    d.slots = c->sparse_slots;
+  if (!rc && c->dense_len && !d.d_cnt && !(rc = zeroed(&d.d_cnt, c->dense_len)) &&
+      !(rc = zeroed(&d.d_byt, c->dense_len)))
+    d.bins = c->dense_len;
+  if (!rc && d.bins_out_cap < c->dense_len) {
+    dev_free(c, d.d_bins_out);
+    d.bins_out_cap = 0;
+    if (!(rc = dev_alloc(c, &d.d_bins_out, c->dense_len * kDenseDeltaWords))) d.bins_out_cap = c->dense_len;
+  }
+  if (rc) {
+    delta_drop(c);
+    return rc;
+  }
+  // from here on the shadow moves: a failure drops the baseline, so nothing is lost for good
+  auto failed = [&](int code) {
+    delta_drop(c);
+    return code;
+  };
+  // changed entries: the carried ones, then the table's
+  std::vector<uint64_t> ent;
+  ent.swap(d.carry);
+  const uint64_t carried = ent.size() / kSparseEntryWords;
+  uint64_t nsp = 0;
+  if ((rc = delta_scan_sparse(c, ent, &nsp))) return failed(rc);
+  // changed dense bins, scattered into zeroed arrays the render walks as it does the counters
+  std::vector<uint64_t> dc(c->dense_len, 0), db(c->dense_len, 0);
+  uint64_t nb = 0;
+  if (c->dense_len) {
+    if (c->cpu) {
+      nb = cpu::dense_delta(c->d_dense_cnt, c->d_dense_byt, d.d_cnt, d.d_byt, c->dense_len, d.d_bins_out,
+                            d.bins_out_cap);
+    } else {
+      hipError_t e = x_set_async(c, d.d_ctr, 0, 8, c->stream);
+      ENQ(c);
+      if (e == hipSuccess)
+        e = launch_dense_delta(c->d_dense_cnt, c->d_dense_byt, d.d_cnt, d.d_byt, c->dense_len, d.d_bins_out,
+                               d.bins_out_cap, d.d_ctr, c->stream);
+      if (e == hipSuccess) e = x_copy_async(c, &nb, d.d_ctr, 8, hipMemcpyDeviceToHost, c->stream);
+      if (e == hipSuccess) e = x_sync(c, c->stream);
+      if (e != hipSuccess) return failed(fail(c, GPUAGG_EDEVICE, "dense delta scan: %s", hipGetErrorString(e)));
+    }
+    if (nb > d.bins_out_cap)
+      return failed(fail(c, GPUAGG_ESTATE, "dense delta scan emitted %llu bins of %zu", (unsigned long long)nb,
+                         c->dense_len));
+    std::vector<uint64_t> bins(nb * kDenseDeltaWords);
+    if (nb && x_copy(c, bins.data(), d.d_bins_out, bins.size() * 8, hipMemcpyDeviceToHost) != hipSuccess)
+      return failed(fail(c, GPUAGG_EDEVICE, "dense delta copy failed"));
+    for (uint64_t i = 0; i < nb; ++i) {
+      const uint64_t *w = &bins[i * kDenseDeltaWords];
+      if (w[0] >= c->dense_len) return failed(fail(c, GPUAGG_ESTATE, "dense delta names bin %llu", (unsigned long long)w[0]));
+      dc[w[0]] = w[1];
+      db[w[0]] = w[2];
+    }
+  }
+  d.slots_scanned = c->sparse_slots;
+  d.bins_scanned = c->dense_len;
+  d.changed_entries = carried + nsp;
+  d.changed_bins = nb;
+  d.rebases += fresh ? 1 : 0;
+
+  auto *r = new gpuagg_result();
+  r->dropped = c->stats.sparse_dropped;  // (cumulative, as gpuagg_sync just read it)
+  if ((rc = render_series(c, dc, db, ent, ent.size() / kSparseEntryWords, r, true))) {
+    gpuagg_result_free(r);
+    return failed(rc);
+  }
+  if (rebased) *rebased = fresh ? 1 : 0;
+  *out = r;
+  return GPUAGG_OK;
+}
+
+int gpuagg_delta_info(gpuagg_ctx *c, uint64_t *slots_scanned, uint64_t *bins_scanned, uint64_t *changed_entries,
+                      uint64_t *changed_bins, uint64_t *rebases) {
+  if (!c) return GPUAGG_EINVAL;
+  if (slots_scanned) *slots_scanned = c->delta.slots_scanned;
+  if (bins_scanned) *bins_scanned = c->delta.bins_scanned;
+  if (changed_entries) *changed_entries = c->delta.changed_entries;
+  if (changed_bins) *changed_bins = c->delta.changed_bins;
+  if (rebases) *rebases = c->delta.rebases;
   return GPUAGG_OK;
 }
 

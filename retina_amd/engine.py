@@ -412,6 +412,40 @@ class GpuAgg:
     def snapshot(self) -> Dict[SeriesKey, int]:
         r = C.c_void_p()
         self._check(self.lib.gpuagg_snapshot(self.h, C.byref(r)))
+        return self._result_series(r)
+
+    def snapshot_delta(self) -> Tuple[Dict[SeriesKey, int], bool]:
+        """The series that changed since the previous snapshot_delta() with their increments,
+        and whether the delta is rebased: True means the increments are relative to zero and
+        replace what the caller accumulated (the first call; after reset() or a reconcile
+        that reset the state), False means they add to it (gpuagg_snapshot_delta)."""
+        r = C.c_void_p()
+        rebased = C.c_int()
+        self._check(self.lib.gpuagg_snapshot_delta(self.h, C.byref(r), C.byref(rebased)))
+        return self._result_series(r), bool(rebased.value)
+
+    def snapshot_delta_count(self) -> Tuple[int, bool]:
+        """snapshot_delta() without walking the series: (their number, rebased).  The delta
+        is consumed all the same."""
+        r = C.c_void_p()
+        rebased = C.c_int()
+        self._check(self.lib.gpuagg_snapshot_delta(self.h, C.byref(r), C.byref(rebased)))
+        try:
+            self.last_dropped = int(self.lib.gpuagg_result_dropped(r))
+            return int(self.lib.gpuagg_result_count(r)), bool(rebased.value)
+        finally:
+            self.lib.gpuagg_result_free(r)
+
+    def delta_info(self) -> Dict[str, int]:
+        """Of the last snapshot_delta(): slots and bins scanned, changed entries and bins the
+        scan emitted, and the rebased deltas since create (gpuagg_delta_info)."""
+        w = [C.c_uint64() for _ in range(5)]
+        self._check(self.lib.gpuagg_delta_info(self.h, *[C.byref(x) for x in w]))
+        names = ("slots_scanned", "bins_scanned", "changed_entries", "changed_bins", "rebases")
+        return {k: x.value for k, x in zip(names, w)}
+
+    def _result_series(self, r) -> Dict[SeriesKey, int]:
+        """A result's series as a dict (sets last_dropped); frees the result."""
         out: Dict[SeriesKey, int] = {}
         self.last_dropped = 0
         try:
@@ -422,11 +456,19 @@ class GpuAgg:
             names = C.POINTER(C.c_char_p)()
             vals = C.POINTER(C.c_char_p)()
             v = C.c_uint64()
+            series = self.lib.gpuagg_result_series
+            refs = (C.byref(metric), C.byref(nl), C.byref(names), C.byref(vals), C.byref(v))
+            fams: Dict[int, Tuple[str, List[str]]] = {}  # a family's metric and label names, decoded once
             for i in range(n):
-                self._check(self.lib.gpuagg_result_series(r, i, C.byref(metric), C.byref(nl),
-                                                          C.byref(names), C.byref(vals), C.byref(v)))
-                labels = tuple((names[j].decode(), vals[j].decode()) for j in range(nl.value))
-                out[(metric.value.decode(), labels)] = v.value
+                rc = series(r, i, *refs)
+                if rc:
+                    self._check(rc)
+                k = nl.value
+                at = C.cast(metric, C.c_void_p).value  # (the family's own name string)
+                fam = fams.get(at)
+                if fam is None:
+                    fam = fams[at] = (metric.value.decode(), [x.decode() for x in names[:k]])
+                out[(fam[0], tuple(zip(fam[1], [x.decode() for x in vals[:k]])))] = v.value
         finally:
             self.lib.gpuagg_result_free(r)
         return out
