@@ -29,6 +29,7 @@ class Config(C.Structure):
                 ("cms_width_log2", C.c_uint32), ("hll_precision", C.c_uint32),
                 ("flags", C.c_uint32), ("wide_list_mib", C.c_uint32), ("latency_limit", C.c_uint32)]
 FLAG_NO_LDS_IP_TABLE = 1
+FLAG_DIRECT_SKETCH = 2  # diagnostics: sketch updates as global atomics, no window lists (nor compact-key segment lists)
 FLAG_FOLD_PER_BATCH = 8  # diagnostics: fold the lists after every batch
 FLAG_NO_HOT_KEYS = 16  # diagnostics: no LDS hot-key cache in front of the group-by table
 FLAG_LDS_CUCKOO = 64  # diagnostics: cuckoo LDS IP image even when the radix image fits

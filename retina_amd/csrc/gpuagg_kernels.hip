@@ -2306,7 +2306,10 @@ __global__ __launch_bounds__(1024) void sketch_scatter_kernel(SketchK k) {
 // position past the capacity falls back to the global atomic (exact).
 // kIp: source lookup 0 HBM table, 1 LDS cuckoo image, 2 LDS radix image, 3 LDS dense radix
 // image.
-// kD: count-min depth fixed at compile time (4), or 0 = k.depth.
+// kD: count-min depth fixed at compile time (4), or 0 = k.depth, at most kStageMaxDepth (a
+// record's updates are held in registers, unrolled over that many rows; launch_sketch
+// sends deeper sketches to the unstaged kernel).
+constexpr int kStageMaxDepth = 8;
 __host__ __device__ inline uint32_t stage_words(uint32_t nwin, uint32_t hnsup, uint32_t sbc, uint32_t sbh) {
   // rc, rb per window + hc, hb per super-window; u16 rings (+ one dummy u32); u32 rings
   // (+ 64 dummies)
@@ -2368,7 +2371,7 @@ __global__ __launch_bounds__(1024) void sketch_stage_kernel(SketchK k) {
   // R records of this lane (act: real records) through every update: all positions
   // reserved first, then the ring stores (dummy entries absorb the rest), then the rare
   // overflow path for the whole wave at once
-  constexpr int kMaxD = kD ? kD : 8;
+  constexpr int kMaxD = kD ? kD : kStageMaxDepth;
   auto records = [&](auto R, const uint32_t *s, const uint32_t *d, const uint32_t *pt, const uint32_t *mt,
                      const bool *act) {
     constexpr int NR = decltype(R)::value;
@@ -2797,9 +2800,12 @@ hipError_t launch_sketch(const SketchArgs &a, hipStream_t st, std::string *kerne
                                         (uintptr_t)(k.ports ? k.ports : k.src)) % 16 == 0;
   // staged scatter: rings sized for a round's mean appends x 1.5 + 64 (the overflow goes
   // straight to the list), flushed every 4 records per lane, or every 2 when the 4-record
-  // rings do not fit; sources looked up in the radix image when the pod IPs allow one
+  // rings do not fit; sources looked up in the radix image when the pod IPs allow one.
+  // Depths above kStageMaxDepth take the unstaged kernel: the staged one would stop at
+  // its unrolled rows and leave the rows above them at zero.
   bool staged = !scatter;  // a fold-only call launches no scatter
-  if (scatter && vec && (!a.cms_depth || a.nwin) && (!a.hll_p || a.hll_nsup) && (a.nwin || a.hll_nsup)) {
+  if (scatter && vec && a.cms_depth <= (uint32_t)kStageMaxDepth && (!a.cms_depth || a.nwin) &&
+      (!a.hll_p || a.hll_nsup) && (a.nwin || a.hll_nsup)) {
     const int ip_kind = lds_ip ? (a.ipl_dense ? 3 : a.ipl_radix ? 2 : 1) : 0;
     if (lds_ip) {
       k.ipl_npfx = a.ipl_npfx;

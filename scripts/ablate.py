@@ -28,6 +28,7 @@ import torch  # noqa: E402
 
 from bench import gen_device_records  # noqa: E402
 from retina_amd import GpuAgg  # noqa: E402
+from retina_amd import _abi  # noqa: E402
 from retina_amd import workloads as W  # noqa: E402
 
 FWD = W.LOCAL_FWD_DROP[:2]
@@ -116,9 +117,9 @@ def main():
         run("c3-none", W.LOCAL_FWD_DROP, pods, cols3, n3)
         run("c3", W.LOCAL_FWD_DROP, pods, cols3, n3, **cms, hll_precision=14)
         run("c3-cms", W.LOCAL_FWD_DROP, pods, cols3, n3, **cms)
-        run("c3-cms-direct", W.LOCAL_FWD_DROP, pods, cols3, n3, flags=2, **cms)
+        run("c3-cms-direct", W.LOCAL_FWD_DROP, pods, cols3, n3, flags=_abi.FLAG_DIRECT_SKETCH, **cms)
         run("c3-hll", W.LOCAL_FWD_DROP, pods, cols3, n3, hll_precision=14)
-        run("c3-hll-direct", W.LOCAL_FWD_DROP, pods, cols3, n3, flags=2, hll_precision=14)
+        run("c3-hll-direct", W.LOCAL_FWD_DROP, pods, cols3, n3, flags=_abi.FLAG_DIRECT_SKETCH, hll_precision=14)
         del cols3
         cols = None
     if not ONLY or any(v.startswith("c5") for v in ONLY):  # C5 spec split by metric

@@ -174,6 +174,34 @@ def test_sketches_bit_exact(gpu_device):
     g.close()
 
 
+NO_LISTS = [c for c in CASES if c[0] in ("c5-local", "local-all6")]
+
+
+@pytest.mark.parametrize("cid,sp,remote,gen", NO_LISTS, ids=[c[0] for c in NO_LISTS])
+def test_parity_without_segment_lists(gpu_device, cid, sp, remote, gen):
+    """FLAG_DIRECT_SKETCH also switches the group-by segment lists off: C5's DNS keys go
+    through aggregate_kernel and sparse_add_compact straight into the table, as they
+    otherwise do only above kSparseMaxSegLists segments."""
+    from retina_amd import GpuAgg, _abi
+    from .helpers import make_engine, to_device
+    pods = W.make_pods(400, seed=11)
+    recs = W.gen_records(30_000, pods, seed=zlib.crc32(cid.encode()) & 0xFFFF, **gen)
+    want = oracle_series(recs, pods, sp, remote)
+    g = make_engine(pods, sp, remote, gpu_device, recs, flags=_abi.FLAG_DIRECT_SKETCH)
+    try:
+        ts = to_device(recs, gpu_device)
+        g.submit_device(GpuAgg.device_columns(*ts), len(recs))
+        g.sync()
+        kernel = g.kernel_name()
+        got = g.snapshot()
+        dropped = g.stats()["sparse_dropped"]
+    finally:
+        g.close()
+    assert got == want, diff_series(got, want)
+    assert kernel == "aggregate_kernel<true, false>", kernel
+    assert dropped == 0
+
+
 TIER0 = [c for c in CASES if c[0] in ("local-dense-ns-pod", "local-dense-workload", "odd-rows-local")]
 
 

@@ -1,8 +1,10 @@
 """Count-min and HyperLogLog on the GPU at the C3 sketch shape (d=4, w=2^20, p=14).
 
 * state bit-exact against the numpy restatement (oracle/sketch.py), through the
-  windowed count-min scatter/fold pass, including list overflow (Zipf-skewed 5-tuples
-  push single windows past their list capacity, which falls back to global atomics);
+  windowed count-min scatter/fold pass under Zipf-skewed 5-tuples (the staging rings
+  overflow into the lists; the lists themselves, sized for 2^22 records per workgroup
+  while folds are deferred, do not fill up here: lists past their capacity are
+  sketch_cases.list_overflow, run by test_gpu_sketch_shapes.py::test_list_overflow);
 * estimates within the stated bounds (BASELINE.json north_star): count-min never
   under-counts and over-counts by more than eps*N = (e/w)*N for at most delta = e^-d of
   the keys; HLL relative error per pod within 4 sigma, sigma = 1.04/sqrt(2^p).
@@ -17,6 +19,7 @@ from oracle import sketch as S
 from retina_amd import workloads as W
 
 from .helpers import make_engine, to_device
+from .sketch_cases import src_slots as _src_slots
 
 pytestmark = pytest.mark.gpu
 
@@ -34,17 +37,6 @@ def _run(recs, pods, gpu_device, d=4, w=20, p=14, flags=0):
         g.close()
 
 
-def _src_slots(pods, src):
-    ip_slot = {}
-    for s, ep in enumerate(pods.endpoints):
-        for ip in ep.ips:
-            ip_slot[int(ip)] = s
-    lut_ips = np.array(sorted(ip_slot), np.uint32)
-    lut_slot = np.array([ip_slot[int(x)] for x in lut_ips], np.int64)
-    pos = np.clip(np.searchsorted(lut_ips, src), 0, len(lut_ips) - 1)
-    return np.where(lut_ips[pos] == src, lut_slot[pos], -1)
-
-
 # source lookups through each LDS image form: dense radix (default), radix with its row
 # table (FLAG_ROW_RADIX), bucketized cuckoo (FLAG_LDS_CUCKOO)
 @pytest.mark.parametrize("flags", [0, 256, 64], ids=["dense-radix", "row-radix", "cuckoo"])
@@ -52,7 +44,7 @@ def _src_slots(pods, src):
 def test_c3_shape_bit_exact(gpu_device, zipf, flags):
     pods = W.make_pods(200, seed=41)
     recs = W.gen_records(3_000_000, pods, seed=42, udp_frac=0.2, zipf=zipf)
-    if zipf:  # heavy 5-tuples: repeat a few flows so some count-min windows overflow
+    if zipf:  # heavy 5-tuples: one flow repeated, so single windows overflow their staging rings
         hot = np.random.default_rng(1).integers(0, 64, len(recs)) == 0
         recs.dst_ip[hot] = recs.dst_ip[0]
         recs.src_ip[hot] = recs.src_ip[0]
