@@ -21,23 +21,29 @@ def harness(tmp_path_factory):
     return exe
 
 
-def run_sets(exe, sets):
+def run_sets(exe, sets, probes=None):
+    """probes: per set, IPs that are in no entry (x*absent: how many of them resolved to a
+    slot in the cuckoo, the radix and the dense radix image)."""
     lines = [str(len(sets))]
-    for ents in sets:
+    for i, ents in enumerate(sets):
         lines.append(str(len(ents)))
         lines.extend("%d %d" % (ip, sl) for ip, sl in ents)
+        listed = probes[i] if probes is not None else []
+        lines.append(str(len(listed)))
+        lines.extend(str(ip) for ip in listed)
     out = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True,
                          check=True).stdout.split("\n")
     res = []
     for ln in out:
         if ln.strip():
             (built, nb, seed, nbytes, load, found, absent, rbuilt, npfx, nblk, rbytes, rfound, rabsent,
-             dbuilt, dnblk, dbytes, dfound, dabsent) = ln.split()
+             dbuilt, dnblk, dbytes, dfound, dabsent, xabsent, xrabsent, xdabsent) = ln.split()
             res.append(dict(built=int(built), nb=int(nb), bytes=int(nbytes), load=float(load),
                             found=int(found), absent=int(absent), rbuilt=int(rbuilt), npfx=int(npfx),
                             nblk=int(nblk), rbytes=int(rbytes), rfound=int(rfound), rabsent=int(rabsent),
                             dbuilt=int(dbuilt), dnblk=int(dnblk), dbytes=int(dbytes), dfound=int(dfound),
-                            dabsent=int(dabsent)))
+                            dabsent=int(dabsent), xabsent=int(xabsent), xrabsent=int(xrabsent),
+                            xdabsent=int(xdabsent)))
     return res
 
 
