@@ -476,7 +476,7 @@ void Engine::latency(const LatArgs &a, uint32_t enabled) {
     const uint64_t k0 = role == 1u ? ((uint64_t)s | ((uint64_t)d << 32)) : ((uint64_t)d | ((uint64_t)s << 32));
     const uint64_t k1 = role == 1u ? ((uint64_t)sp | ((uint64_t)dp << 16) | (id << 32))
                                    : ((uint64_t)dp | ((uint64_t)sp << 16) | (id << 32));
-    const uint32_t verdict = (m >> 8) & 0xFFu, flags = (m >> 21) & 0x3Fu;
+    const uint32_t verdict = meta_verdict(m), flags = meta_flags(m);  // (verdict 0 is FORWARDED)
     const bool has_flags = verdict == kVerdictForwarded || verdict == kVerdictRetrans;
     const bool syn = has_flags && (flags & 2u), ack = has_flags && (flags & 16u);
     const uint32_t nanos = (uint32_t)(a.time_ns[i] % 1000000000ULL);

@@ -148,6 +148,12 @@ GA_HD uint64_t fmix64(uint64_t k) {
   k ^= k >> 33;
   return k;
 }
+// The latency join's sort key (gpuagg_latency.hip): the exact key is {k0 = the request's
+// src | dst << 32, k1 = sport | dport << 16 | tcp_id << 32}; equal hashes of different
+// keys share a segment of the walk.
+GA_HD uint64_t lat_hash(uint64_t k0, uint64_t k1) {
+  return fmix64(k0 ^ fmix64(k1 ^ 0x9E3779B97F4A7C15ULL));
+}
 
 // dist.shard_of (retina_amd/dist.py), the Go plugin's shardOf and the feeds: fmix64 of the
 // direction-free 5-tuple -- lo <= hi the two (ip << 16 | port) ends, so a request and its

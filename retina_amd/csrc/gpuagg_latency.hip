@@ -62,10 +62,6 @@ __device__ __forceinline__ uint32_t lat_role(const LatArgs &a, const uint32_t *a
   return (lat_is_api(api, a.n_api, a.src[i]) || lat_is_api(api, a.n_api, a.dst[i])) ? role : 0u;
 }
 
-__device__ __forceinline__ uint64_t lat_hash(uint64_t k0, uint64_t k1) {
-  return fmix64(k0 ^ fmix64(k1 ^ 0x9E3779B97F4A7C15ULL));
-}
-
 // The unit of the front end is one wave over a contiguous record range (a.chunk rows):
 // the count pass reads meta, tcp_id and time for every row (src / dst only for TCP rows
 // with a TCP id at observation point 2 or 3), the scan gives each unit its first event
@@ -184,8 +180,9 @@ __global__ __launch_bounds__(kLatThreads) void lat_emit_kernel(LatArgs a) {
       const uint64_t k0 = role == kRoleReq ? ((uint64_t)s | ((uint64_t)d << 32)) : ((uint64_t)d | ((uint64_t)s << 32));
       const uint64_t k1 = role == kRoleReq ? ((uint64_t)sp | ((uint64_t)dp << 16) | (id << 32))
                                            : ((uint64_t)dp | ((uint64_t)sp << 16) | (id << 32));
-      const uint32_t m8 = a.meta[i], verdict = (m8 >> 8) & 0xFFu, flags = (m8 >> 21) & 0x3Fu;
-      // AddTCPFlags: packetparser sets them on every TCP flow (forwarded); SYN bit 1, ACK bit 4
+      const uint32_t m8 = a.meta[i], verdict = meta_verdict(m8), flags = meta_flags(m8);
+      // AddTCPFlags: packetparser sets them on every TCP flow (forwarded, which is also what
+      // ToFlow makes of verdict 0); SYN bit 1, ACK bit 4
       const bool has_flags = verdict == kVerdictForwarded || verdict == kVerdictRetrans;
       const uint32_t bits = role | ((has_flags && (flags & 2u)) ? 4u : 0u) | ((has_flags && (flags & 16u)) ? 8u : 0u);
       const uint64_t e = base + rank;
