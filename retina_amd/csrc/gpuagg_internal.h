@@ -226,8 +226,8 @@ constexpr uint64_t kLdsBytesMask = kLdsCountOne - 1;
 constexpr uint64_t kMaxRecordsPerBlock = (1ULL << 20) - 4;  // count field < 2^20, multiple of 4
 // fold windows: 2^13 u64 bins (64 KiB of LDS, two fold workgroups per CU) so a spilled
 // bin's window is a shift.  Spill entries are u32: the bin's offset in its window
-// (13 bits) | bytes << 13; a packet of >= 2^19 bytes adds its bytes with a global
-// atomic and spills 0.
+// (13 bits) | bytes << 13 (18 bits: bit 31 is kSpillRowMask); a packet of >= 2^18 bytes
+// adds its bytes with a global atomic and spills 0.
 constexpr uint32_t kFoldWindowShift = 13, kFoldWindowBins = 1u << kFoldWindowShift;
 // Bit 31 of a spill entry marks a row-mask entry: offset = the first bin of an 8-bin
 // tcpflags row, bits [win_shift, win_shift + 8) = the flags to count (+1 each); plain

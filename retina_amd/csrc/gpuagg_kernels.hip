@@ -3680,7 +3680,8 @@ hipError_t launch_aggregate(const LaunchArgs &a, hipStream_t st, hipEvent_t betw
                variant >= 200 ? a.sig : 0u, a.ipl_dense ? 2 : a.ipl_radix ? 1 : 0);
     else if (a.dense_ng)
       snprintf(name, sizeof name, "dense_local_kernel<%u, %s, %s, %uu%s>", a.dense_ng, a.vec ? "true" : "false",
-               a.dns_compact ? "true" : "false", variant >= 305 ? a.sig : 0u, variant == 306 ? ", true" : "");
+               a.dns_compact ? "true" : "false", variant == 305 || variant == 306 ? a.sig : 0u,
+               variant == 306 ? ", true" : "");
     else
       snprintf(name, sizeof name, "aggregate_kernel<%s, %s>", a.vec ? "true" : "false", sketch ? "true" : "false");
     *kernel = name;
