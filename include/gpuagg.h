@@ -564,7 +564,12 @@ int gpuagg_submit_enrich(gpuagg_ctx *ctx, gpuagg_batch *batch, size_t n, int32_t
  * Hubble consumers from them (labels and strings stay on the host).
  * ---------------------------------------------------------------------------- */
 /* The ipcache image: IP -> identity (ipcache.LookupByIP) and a caller-assigned K8s
- * metadata id (GetK8sMetadata: pod, namespace; 0xFFFFFFFF = none).  Replaces the image. */
+ * metadata id (GetK8sMetadata: pod, namespace; 0xFFFFFFFF = none).  Replaces the image;
+ * n = 0 installs an empty one (every address resolves to World), and the last entry for an
+ * address wins.  255.255.255.255 marks a free slot of the image and cannot be a key: a set
+ * that holds it is refused with GPUAGG_ERANGE and the image before it stays in force.  A
+ * record with that address (every DHCP discover) therefore always misses: World, no
+ * metadata. */
 int gpuagg_ipcache_set(gpuagg_ctx *ctx, const uint32_t *ipv4, const uint32_t *identity,
                        const uint32_t *meta_id, size_t n);
 

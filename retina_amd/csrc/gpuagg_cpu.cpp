@@ -384,12 +384,12 @@ void Engine::hubble(const HubbleArgs &a) {
     uint32_t h = ip_h1(ip, a.seed) & a.mask;
     for (uint32_t p = 0; p <= a.max_probe; ++p, h = (h + 1) & a.mask) {
       const uint4 e = a.table[h];
+      if (e.x == kIpcEmpty) return;  // a free slot ends the probe before it can match
       if (e.x == ip) {
         id = e.y;
         meta = e.z;
         return;
       }
-      if (e.x == kIpcEmpty) return;
     }
   };
   parallel(threads_, a.n, [&](unsigned, size_t lo, size_t hi) {

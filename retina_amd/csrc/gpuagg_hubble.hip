@@ -24,8 +24,8 @@ __device__ __forceinline__ uint2 ipc_lookup(const HubbleArgs &a, uint32_t ip) {
   uint32_t h = ip_h1(ip, a.seed) & a.mask;
   for (uint32_t p = 0; p <= a.max_probe; ++p, h = (h + 1) & a.mask) {
     const uint4 e = a.table[h];
+    if (e.x == kIpcEmpty) break;  // a free slot ends the probe before it can match (255.255.255.255)
     if (e.x == ip) return make_uint2(e.y, e.z);
-    if (e.x == kIpcEmpty) break;
   }
   return make_uint2(kIdentityWorld, kIpcNoMeta);  // LookupByIP miss: World, no metadata
 }

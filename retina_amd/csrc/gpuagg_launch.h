@@ -9,6 +9,7 @@
 #include <stdint.h>
 
 #include "gpuagg_internal.h"
+#include "ipc_build.h"
 
 namespace gpuagg {
 
@@ -134,8 +135,11 @@ struct EnrichArgs {
 };
 hipError_t launch_enrich(const EnrichArgs &a, uint32_t n_cu, hipStream_t st);
 
-// Hubble-mode L3/L4 enrichment (gpuagg_hubble.hip).
-constexpr uint32_t kIpcEmpty = 0xFFFFFFFFu, kIpcNoMeta = 0xFFFFFFFFu, kIdentityWorld = 2;
+// Hubble-mode L3/L4 enrichment (gpuagg_hubble.hip).  kIpcEmpty (ipc_build.h, with the
+// image's builder) is the key of a free slot, so a probe tests "free" before "equal": a free
+// slot ends the probe and never matches, and 255.255.255.255 -- which gpuagg_ipcache_set
+// refuses as a key -- resolves to World with no metadata like any other absent address.
+constexpr uint32_t kIpcNoMeta = 0xFFFFFFFFu, kIdentityWorld = 2;
 enum : uint32_t { kSummaryNone = 0, kSummaryTcp = 1, kSummaryUdp = 2, kSummaryDrop = 3, kSummaryDns = 4 };
 struct HubbleArgs {
   const uint4 *table;  // (ip, identity, metadata id, 0); ip kIpcEmpty = free

@@ -5185,22 +5185,10 @@ int gpuagg_ipcache_set(gpuagg_ctx *c, const uint32_t *ipv4, const uint32_t *iden
   if (!c || (n && (!ipv4 || !identity || !meta_id))) return GPUAGG_EINVAL;
   int rc = bind(c);
   if (rc) return rc;
-  // open addressing, linear probing, load <= 50 %; the last entry for an IP wins
-  size_t cap = 64;
-  while (cap < 2 * n) cap <<= 1;
-  const uint32_t seed = 0x7F4A7C15u, mask = (uint32_t)(cap - 1);
-  std::vector<uint4> tab(cap, uint4{kIpcEmpty, 0u, 0u, 0u});
-  uint32_t max_probe = 0;
-  for (size_t i = 0; i < n; ++i) {
-    if (ipv4[i] == kIpcEmpty) return fail(c, GPUAGG_ERANGE, "255.255.255.255 cannot be an ipcache key");
-    uint32_t h = ip_h1(ipv4[i], seed) & mask, p = 0;
-    while (tab[h].x != kIpcEmpty && tab[h].x != ipv4[i]) {
-      h = (h + 1) & mask;
-      ++p;
-    }
-    tab[h] = uint4{ipv4[i], identity[i], meta_id[i], 0u};
-    max_probe = std::max(max_probe, p);
-  }
+  IpcImage img;  // (ipc_build.h: the table's form and the last-wins rule)
+  if (!ipc_build(ipv4, identity, meta_id, n, &img))
+    return fail(c, GPUAGG_ERANGE, "255.255.255.255 cannot be an ipcache key");
+  const size_t cap = img.tab.size();
   HIPCHK(c, x_sync(c, c->stream));  // in-flight decodes read the old image
   if (cap != c->ipc_cap) {
     dev_free(c, c->d_ipc);
@@ -5208,9 +5196,9 @@ int gpuagg_ipcache_set(gpuagg_ctx *c, const uint32_t *ipv4, const uint32_t *iden
     if ((rc = dev_alloc(c, &c->d_ipc, cap))) return rc;
     c->ipc_cap = cap;
   }
-  HIPCHK(c, x_copy(c, c->d_ipc, tab.data(), cap * sizeof(uint4), hipMemcpyHostToDevice));
-  c->ipc_seed = seed;
-  c->ipc_max_probe = max_probe;
+  HIPCHK(c, x_copy(c, c->d_ipc, img.tab.data(), cap * sizeof(uint4), hipMemcpyHostToDevice));
+  c->ipc_seed = kIpcSeed;
+  c->ipc_max_probe = img.max_probe;
   return GPUAGG_OK;
 }
 

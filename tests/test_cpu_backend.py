@@ -1,8 +1,9 @@
 """The CPU backend (GPUAGG_FLAG_CPU_BACKEND, retina_amd/csrc/gpuagg_cpu.cpp): the same
 C ABI on host threads for nodes without a gfx950 device.  Runs here (no GPU) against the
 oracle with the GPU parity cases, and covers the other entry points the Go plugin uses:
-raw perf-record decode, sketches, node-apiserver latency, enriched flows, Hubble decode,
-the multi-context merge and slot retirement."""
+raw perf-record decode, sketches, node-apiserver latency, enriched flows, the multi-context
+merge and slot retirement.  (The Hubble decode on this backend, and the decode and enrich
+entry points at their edges: tests/test_emit_cases_cpu.py.)"""
 
 import zlib
 
