@@ -34,6 +34,7 @@ import (
 	"math/bits"
 	"net"
 	"os"
+	"sort"
 	"strconv"
 	"strings"
 	"sync"
@@ -79,6 +80,10 @@ const (
 	// (2^22 entries, 160 MiB: one launch of packetCapacity samples at one update each).
 	sparseLog2    = 20
 	sparseMaxLog2 = 26
+	// count-min geometry when HeavyHitterMinCount is set: 4 rows of 2^20 columns (16 MiB per
+	// device; the candidate table is the library's default, 2^16 slots of 20 B)
+	sketchDepth     = 4
+	sketchWidthLog2 = 20
 	channelDepth  = 10000 // like packetparser's recordsChannel (types_linux.go:37-38)
 	pieceDepth    = 16    // full pieces of rawPiece waiting for Start (1M samples)
 )
@@ -181,6 +186,21 @@ type gpuAgg struct {
 	noResponse *prometheus.CounterVec
 	noRespLast float64
 	lostLast   uint64 // gpuagg_result_dropped of the previous publish (cumulative since reset)
+
+	// Sketch readouts, off by default; set before Init.  HeavyHitterMinCount != 0 creates the
+	// contexts with a count-min sketch (sketchDepth x 2^sketchWidthLog2) and turns the
+	// candidate pass on (gpuagg_set_heavy_hitters): HeavyHitters then answers.
+	// DistinctPeerPrecision != 0 (HyperLogLog p, 4..18) gives every source pod its registers:
+	// DistinctPeers then answers.  Nothing is published from either.
+	HeavyHitterMinCount   uint32
+	DistinctPeerPrecision uint32
+}
+
+// HeavyHitter is one flow of HeavyHitters: the 5-tuple in the record encoding and the
+// count-min estimate of its records (never below the true count).
+type HeavyHitter struct {
+	SrcIP, DstIP, Ports, Proto uint32
+	Estimate                   uint64
 }
 
 type dnsPayload struct {
@@ -383,6 +403,10 @@ func (g *gpuAgg) Init() error {
 		cfg := C.gpuagg_config{
 			abi_version: C.GPUAGG_ABI_VERSION, device: C.int32_t(dev), remote_context: remote,
 			max_slots: maxSlots, max_ips: 2 * maxSlots, sparse_capacity_log2: sparseLog2, flags: flags,
+			hll_precision: C.uint32_t(g.DistinctPeerPrecision),
+		}
+		if g.HeavyHitterMinCount != 0 {
+			cfg.cms_depth, cfg.cms_width_log2 = sketchDepth, sketchWidthLog2
 		}
 		d := &device{}
 		if rc := C.gpuagg_create(&cfg, &d.ctx); rc != C.GPUAGG_OK {
@@ -393,6 +417,14 @@ func (g *gpuAgg) Init() error {
 			C.gpuagg_destroy(d.ctx)
 			g.destroyLocked()
 			return err
+		}
+		if g.HeavyHitterMinCount != 0 {
+			if err := check(d.ctx, C.gpuagg_set_heavy_hitters(d.ctx, C.uint32_t(g.HeavyHitterMinCount), 0),
+				"gpuagg_set_heavy_hitters"); err != nil {
+				C.gpuagg_destroy(d.ctx)
+				g.destroyLocked()
+				return err
+			}
 		}
 		if err := check(d.ctx, C.gpuagg_alloc_batch(d.ctx, batchCapacity, &d.batch), "gpuagg_alloc_batch"); err != nil {
 			C.gpuagg_destroy(d.ctx)
@@ -449,6 +481,74 @@ func (g *gpuAgg) Init() error {
 		g.apiSubID = pubsub.New().Subscribe(common.PubSubAPIServer, &fn)
 	}
 	return nil
+}
+
+// HeavyHitters returns the k flows with the largest count-min estimate among the candidates
+// of every device (gpuagg_heavy_hitters), estimate descending, then 5-tuple ascending.
+// Records are sharded by 5-tuple, so a flow's count lives on one device and the devices'
+// lists are simply merged.  Needs HeavyHitterMinCount.
+func (g *gpuAgg) HeavyHitters(k int) ([]HeavyHitter, error) {
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	if k <= 0 {
+		return nil, nil
+	}
+	var all []HeavyHitter
+	buf := make([]C.gpuagg_hh_entry, k)
+	for _, d := range g.devs {
+		var n C.size_t
+		if err := check(d.ctx, C.gpuagg_heavy_hitters(d.ctx, &buf[0], C.size_t(k), &n), "gpuagg_heavy_hitters"); err != nil {
+			return nil, err
+		}
+		for _, e := range buf[:int(n)] {
+			all = append(all, HeavyHitter{SrcIP: uint32(e.src_ip), DstIP: uint32(e.dst_ip), Ports: uint32(e.ports),
+				Proto: uint32(e.proto), Estimate: uint64(e.estimate)})
+		}
+	}
+	sort.Slice(all, func(i, j int) bool {
+		a, b := all[i], all[j]
+		switch {
+		case a.Estimate != b.Estimate:
+			return a.Estimate > b.Estimate
+		case a.SrcIP != b.SrcIP:
+			return a.SrcIP < b.SrcIP
+		case a.DstIP != b.DstIP:
+			return a.DstIP < b.DstIP
+		case a.Ports != b.Ports:
+			return a.Ports < b.Ports
+		}
+		return a.Proto < b.Proto
+	})
+	if len(all) > k {
+		all = all[:k]
+	}
+	return all, nil
+}
+
+// DistinctPeers returns, per device, the distinct-destination estimate of every slot
+// (gpuagg_hll_estimate_all: reduced on the device, 24 bytes per pod cross to the host).  A
+// pod's flows are spread over the devices by 5-tuple, so on a multi-GPU node each device
+// has seen a part of its peers; the estimate over all of them is read from device 0 after
+// the epoch merge.  Needs DistinctPeerPrecision.
+func (g *gpuAgg) DistinctPeers() ([][]float64, error) {
+	g.mu.Lock()
+	defer g.mu.Unlock()
+	out := make([][]float64, 0, len(g.devs))
+	for _, d := range g.devs {
+		var n C.size_t
+		if rc := C.gpuagg_hll_estimate_all(d.ctx, nil, 0, &n); rc != C.GPUAGG_OK && rc != C.GPUAGG_ECAPACITY {
+			return nil, check(d.ctx, rc, "gpuagg_hll_estimate_all")
+		}
+		est := make([]float64, int(n))
+		if n != 0 {
+			if err := check(d.ctx, C.gpuagg_hll_estimate_all(d.ctx, (*C.double)(unsafe.Pointer(&est[0])), n, &n),
+				"gpuagg_hll_estimate_all"); err != nil {
+				return nil, err
+			}
+		}
+		out = append(out, est[:int(n)])
+	}
+	return out, nil
 }
 
 // Reconcile mirrors Module.Reconcile (metrics_module.go:142-203): nothing happens when

@@ -467,6 +467,59 @@ int gpuagg_hll_estimate(gpuagg_ctx *ctx, int32_t slot, double *estimate);
 int gpuagg_cms_copy(gpuagg_ctx *ctx, uint32_t *host_out, size_t n_words);
 int gpuagg_hll_copy(gpuagg_ctx *ctx, uint8_t *host_out, size_t n_bytes);
 
+/* Heavy hitters: which flows the count-min says are large.  Off by default; a ctx that never
+ * calls gpuagg_set_heavy_hitters allocates nothing and runs no extra kernel.
+ *
+ * With min_count != 0, after the records of a submit (any entry: gpuagg_submit, _device,
+ * _raw*, _enrich, the raw feed) are in the count-min rows -- all of them, the waiting
+ * count-min lists folded -- each record of that submit is tested once: its key (src_ip,
+ * dst_ip, ports or 0 without a ports column, proto; what the count-min hashes) becomes a
+ * CANDIDATE iff its estimate at that point is >= min_count.  The candidate set is therefore a
+ * function of the sequence of submits and min_count alone, and since estimates never
+ * under-count, every flow whose true count reaches min_count is a candidate (collisions can
+ * admit more flows, never fewer).
+ *
+ * The candidates are exact 128-bit keys in a device table of 2^capacity_log2 slots (4..24;
+ * 0: 16), 20 bytes a slot.  Size it for twice the candidates expected: it holds at least
+ * 2^(capacity_log2 - 1) distinct keys, and a key a full table refuses is counted (dropped),
+ * never silent.  Needs cms_depth != 0, else GPUAGG_ESTATE; min_count == 0 turns the feature
+ * off and frees the table; changing either value on a live ctx clears the candidates.  Legal
+ * any time after gpuagg_create.  gpuagg_reset and a gpuagg_reconcile that resets the state
+ * clear the candidates and dropped.  gpuagg_merge unions the candidates of ctxs[1..n) into
+ * ctxs[0] (records are sharded by 5-tuple, so a flow's count lives on one GPU and the
+ * guarantee survives); every ctx must have the same min_count, else GPUAGG_EINVAL before
+ * anything is moved. */
+int gpuagg_set_heavy_hitters(gpuagg_ctx *ctx, uint32_t min_count, uint32_t capacity_log2);
+/* Candidates held, insert attempts a full table refused since the last clear, and the two
+ * settings (min_count 0: off).  Any pointer may be NULL. */
+int gpuagg_hh_info(gpuagg_ctx *ctx, uint64_t *candidates, uint64_t *dropped, uint32_t *min_count,
+                   uint32_t *capacity_log2);
+typedef struct gpuagg_hh_entry {
+  uint32_t src_ip, dst_ip, ports, proto;
+  uint64_t estimate;
+} gpuagg_hh_entry;
+/* The min(k, candidates) candidates with the largest CURRENT count-min estimate (computed on
+ * the device, everything pending folded first), by estimate descending, then (src_ip, dst_ip,
+ * ports, proto) ascending as unsigned integers; no key twice; *n = entries written.  Each
+ * estimate is what gpuagg_cms_estimate returns for the key after a gpuagg_sketch_refresh at
+ * this point.  Only the selected entries (and the ties of the k-th) cross to the host; the
+ * rows are not copied.  GPUAGG_ESTATE while the feature is off. */
+int gpuagg_heavy_hitters(gpuagg_ctx *ctx, gpuagg_hh_entry *out, size_t k, size_t *n);
+/* Every candidate key as 4 words (src_ip, dst_ip, ports, proto), in any order, none twice;
+ * *n = candidates, GPUAGG_ECAPACITY (with *n set) when cap keys do not hold them. */
+int gpuagg_hh_candidates(gpuagg_ctx *ctx, uint32_t *keys4, size_t cap, size_t *n);
+/* Inserts n host keys (4 words each) that are not candidates yet: the in-process merge, or a
+ * caller's own all-gather of gpuagg_hh_candidates across processes. */
+int gpuagg_hh_add_candidates(gpuagg_ctx *ctx, const uint32_t *keys4, size_t n);
+
+/* Distinct peers of every pod in one call: *n = HLL rows (hll_len >> p), out[s] = the
+ * estimate of slot s -- gpuagg_hll_estimate's estimator, linear counting included -- from the
+ * live device registers, everything pending folded first.  The registers are reduced on the
+ * device (24 bytes per pod cross to the host), no copy of them is made and no
+ * gpuagg_sketch_refresh is needed.  A pod that has sent nothing gives exactly 0.0.
+ * GPUAGG_ESTATE without HLL; GPUAGG_ECAPACITY (with *n set) when cap < *n. */
+int gpuagg_hll_estimate_all(gpuagg_ctx *ctx, double *out, size_t cap, size_t *n);
+
 /* ------------------------------------------------------------------------------
  * Multi-GPU merge (one process per GPU).  Mergeable device state is exposed so the
  * caller's collective (RCCL through torch.distributed) can reduce it in place:

@@ -97,6 +97,10 @@ FEED_DRY_RUN = 0x100  # or'ed into a mode: stagings counted, never submitted (di
 LAT_SUM_WORDS = 35  # gpuagg_state_desc.latency: words [0, 35) sum, the rest max (gpuagg.h)
 
 
+# gpuagg_hh_entry as a numpy structured dtype (24 bytes, no padding)
+HH_ENTRY = [("src_ip", "<u4"), ("dst_ip", "<u4"), ("ports", "<u4"), ("proto", "<u4"), ("estimate", "<u8")]
+
+
 KERNEL_NAMES = {0: None, 1: "aggregate_kernel", 2: "dense_local_kernel", 3: "dense_lds_kernel", 4: "cpu"}
 
 
@@ -136,6 +140,12 @@ SIGNATURES = [
     ("gpuagg_hll_estimate", C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]),
     ("gpuagg_cms_copy", C.c_int, [C.c_void_p, u32p, C.c_size_t]),
     ("gpuagg_hll_copy", C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t]),
+    ("gpuagg_set_heavy_hitters", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    ("gpuagg_hh_info", C.c_int, [C.c_void_p, u64p, u64p, u32p, u32p]),
+    ("gpuagg_heavy_hitters", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("gpuagg_hh_candidates", C.c_int, [C.c_void_p, u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("gpuagg_hh_add_candidates", C.c_int, [C.c_void_p, u32p, C.c_size_t]),
+    ("gpuagg_hll_estimate_all", C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_size_t, C.POINTER(C.c_size_t)]),
     ("gpuagg_state", C.c_int, [C.c_void_p, C.POINTER(StateDesc)]),
     ("gpuagg_sparse_export", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     ("gpuagg_sparse_import", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),

@@ -657,5 +657,55 @@ void zero_slots(uint64_t *cnt, uint64_t *byt, uint8_t *hll, uint32_t hll_p, cons
   }
 }
 
+// ---- sketch readouts (gpuagg_hh.hip) -------------------------------------------------------
+namespace {
+uint32_t cms_min(const uint32_t *cms, uint32_t depth, uint32_t wlog2, uint64_t base) {
+  const uint32_t wmask = (1u << wlog2) - 1u;
+  uint32_t m = 0xFFFFFFFFu;
+  for (uint32_t r = 0; r < depth; ++r) m = std::min(m, cms[((size_t)r << wlog2) + cms_col(base, r, wmask)]);
+  return m;
+}
+}  // namespace
+
+void HhSet::add(const uint32_t *keys4, size_t n) {
+  for (size_t i = 0; i < n; ++i) {
+    const std::array<uint32_t, 4> key{keys4[4 * i], keys4[4 * i + 1], keys4[4 * i + 2], keys4[4 * i + 3]};
+    if (keys.count(key)) continue;
+    if (keys.size() >= capacity) ++dropped;
+    else keys.insert(key);
+  }
+}
+
+void HhSet::pass(const ColsView &cols, size_t n, const uint32_t *cms, uint32_t depth, uint32_t wlog2,
+                 uint32_t min_count) {
+  for (size_t i = 0; i < n; ++i) {
+    const uint32_t key[4] = {cols.src_ip[i], cols.dst_ip[i], cols.ports ? cols.ports[i] : 0u, meta_proto(cols.meta[i])};
+    if (cms_min(cms, depth, wlog2, cms_base(key[0], key[1], key[2], key[3])) >= min_count) add(key, 1);
+  }
+}
+
+void HhSet::top(const uint32_t *cms, uint32_t depth, uint32_t wlog2, size_t k, std::vector<HhEntry> &out) const {
+  out.clear();
+  for (const auto &key : keys)  // ascending by key: a stable sort keeps that order among ties
+    out.push_back(HhEntry{key[0], key[1], key[2], key[3], cms_min(cms, depth, wlog2, cms_base(key[0], key[1], key[2], key[3]))});
+  std::stable_sort(out.begin(), out.end(), [](const HhEntry &a, const HhEntry &b) { return a.estimate > b.estimate; });
+  if (out.size() > k) out.resize(k);
+}
+
+void hll_sums(const uint8_t *hll, uint32_t p, uint32_t rows, uint64_t *out3) {
+  const size_t m = (size_t)1 << p;
+  for (uint32_t s = 0; s < rows; ++s) {
+    uint64_t zeros = 0, lo = 0, hi = 0;
+    const uint8_t *reg = hll + ((size_t)s << p);
+    for (size_t i = 0; i < m; ++i) {
+      const uint32_t r = reg[i];
+      zeros += r == 0;
+      if (r <= 32) lo += 1ULL << (32 - r);
+      else if (r <= 64) hi += 1ULL << (64 - r);
+    }
+    out3[3 * (size_t)s] = zeros, out3[3 * (size_t)s + 1] = lo, out3[3 * (size_t)s + 2] = hi;
+  }
+}
+
 }  // namespace cpu
 }  // namespace gpuagg

@@ -2,7 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <memory>
+#include <set>
 #include <string>
 #include <vector>
 #include <stddef.h>
@@ -272,6 +274,56 @@ struct ForkJoin;
 // joined back into st
 hipError_t launch_sketch(const SketchArgs &a, hipStream_t st, std::string *kernels, const ForkJoin *fj = nullptr);
 
+// Sketch readouts (gpuagg_hh.hip): the heavy-hitter candidate table and the per-pod HLL sums.
+// The table: 2^L slots of a 16-byte key (src_ip, dst_ip, ports, proto) and a u32 tag,
+// zeroed when empty; words: kHhWords u64 counters.
+enum : uint32_t {
+  kHhWordDropped = 0,  // insert attempts a full table refused, since the last clear
+  kHhWordCount = 1,    // launch_hh_count: slots that hold a candidate (a key in two slots counted once)
+  kHhWordCursor = 2,   // launch_hh_export's append position
+  kHhWordSelect = 3,   // launch_hh_rank: sorted entries to hand over (the k largest and the ties of the k-th)
+  kHhWords = 4
+};
+struct HhTable {
+  uint4 *keys;
+  uint32_t *tags;
+  uint32_t mask;  // slots - 1
+  uint64_t *words;
+  const uint32_t *cms;
+  uint32_t cms_depth, cms_wlog2;
+};
+struct HhEntry {  // gpuagg_hh_entry
+  uint32_t src_ip, dst_ip, ports, proto;
+  uint64_t estimate;
+};
+struct HhArgs {
+  HhTable table;
+  ColsView cols;  // src_ip, dst_ip, meta, ports (may be null: 0)
+  size_t n;
+  uint64_t chunk;   // records per workgroup, a multiple of 4
+  uint32_t blocks;  // workgroups (one per CU)
+  uint32_t min_count;
+};
+// hh_candidate_kernel over one submit's records, after its count-min updates are in the rows.
+hipError_t launch_hh_candidates(const HhArgs &a, hipStream_t st);
+// Inserts n keys (device, 4 words each) that are not in the table yet.
+hipError_t launch_hh_add(const HhTable &t, const uint32_t *keys4, size_t n, hipStream_t st);
+// Marks a key's second slot, should it have one, and counts the candidates into
+// words[kHhWordCount]; every read below comes after it.
+hipError_t launch_hh_count(const HhTable &t, hipStream_t st);
+// Every candidate key (4 words) into out4[0, cap), in any order.
+hipError_t launch_hh_export(const HhTable &t, uint32_t *out4, size_t cap, hipStream_t st);
+// The candidates ranked by their current estimate: sort keys of every slot into sort_in,
+// sorted (estimate descending, slot ascending) into sort_out, and words[kHhWordSelect] = the
+// sorted entries that hold the kk largest and the ties of the kk-th (1 <= kk <= candidates).
+hipError_t hh_sort_bytes(size_t slots, size_t *bytes);
+hipError_t launch_hh_rank(const HhTable &t, uint64_t *sort_in, uint64_t *sort_out, void *tmp, size_t tmp_bytes,
+                          size_t kk, hipStream_t st);
+hipError_t launch_hh_gather(const HhTable &t, const uint64_t *sorted, size_t m, HhEntry *out, hipStream_t st);
+// hll_estimate_kernel: out3[3 s ..] = pod s's zero registers, sum 2^(32 - r) over r <= 32 and
+// sum 2^(64 - r) over r > 32 of its 2^p registers.
+hipError_t launch_hll_estimate(const uint8_t *hll, uint32_t p, uint32_t rows, uint64_t *out3, hipStream_t st);
+
 // `between` (may be null) is recorded after aggregate_kernel, before the spill fold.
 // *kernel (may be null) receives the aggregation kernel's signature as rocprofv3 prints it
 // without "void gpuagg::" and the argument list, e.g. "dense_lds_kernel<2, true, 41u>".
@@ -350,6 +402,19 @@ size_t dense_delta(const uint64_t *cnt, const uint64_t *byt, uint64_t *sh_cnt, u
                    uint64_t *out, size_t cap);
 void zero_slots(uint64_t *cnt, uint64_t *byt, uint8_t *hll, uint32_t hll_p, const uint32_t *dead, uint32_t ndead,
                 const Plan &p);
+// The heavy-hitter candidate set and its readouts as host loops (gpuagg_hh.hip): at most
+// `capacity` exact keys; an insert a full set refuses is counted in `dropped`.
+struct HhSet {
+  uint64_t capacity = 0, dropped = 0;
+  std::set<std::array<uint32_t, 4>> keys;
+  // hh_candidate_kernel: every record whose count-min estimate has reached min_count
+  void pass(const ColsView &cols, size_t n, const uint32_t *cms, uint32_t depth, uint32_t wlog2, uint32_t min_count);
+  void add(const uint32_t *keys4, size_t n);
+  // the k largest by estimate descending, then key ascending
+  void top(const uint32_t *cms, uint32_t depth, uint32_t wlog2, size_t k, std::vector<HhEntry> &out) const;
+};
+// launch_hll_estimate
+void hll_sums(const uint8_t *hll, uint32_t p, uint32_t rows, uint64_t *out3);
 }  // namespace cpu
 
 }  // namespace gpuagg

@@ -429,6 +429,13 @@ struct gpuagg_ctx {
   size_t hll_len = 0;
   std::vector<uint32_t> h_cms;
   std::vector<uint8_t> h_hll;
+  // heavy hitters (gpuagg_set_heavy_hitters; off while hh_min == 0): the candidate table of
+  // gpuagg_hh.hip -- 2^hh_log2 slots of a 16-byte key and a tag word -- or, CPU backend, a set
+  uint32_t hh_min = 0, hh_log2 = 0;
+  uint4 *d_hh_keys = nullptr;
+  uint32_t *d_hh_tags = nullptr;
+  uint64_t *d_hh_words = nullptr;  // kHhWords
+  gpuagg::cpu::HhSet hh_cpu;
 
   // Device staging for host-fed batches, double-buffered: batch k+1's H2D copy (on
   // copy_stream) overlaps batch k's aggregation (on stream).  `copied` is recorded on
@@ -805,6 +812,31 @@ void drop_pending(gpuagg_ctx *c) {
 
 void delta_drop(gpuagg_ctx *c);
 
+// ---- heavy-hitter candidates (gpuagg_hh.hip) -------------------------------------------------
+HhTable hh_table(const gpuagg_ctx *c) {
+  return HhTable{c->d_hh_keys, c->d_hh_tags, (uint32_t)(((size_t)1 << c->hh_log2) - 1), c->d_hh_words,
+                 c->d_cms,     c->cfg.cms_depth, c->cfg.cms_width_log2};
+}
+// Empties the candidate set and its dropped counter (async on the stream).
+int hh_clear(gpuagg_ctx *c) {
+  if (!c->hh_min) return GPUAGG_OK;
+  if (c->cpu) {
+    c->hh_cpu.keys.clear();
+    c->hh_cpu.dropped = 0;
+    return GPUAGG_OK;
+  }
+  HIPCHK(c, x_set_async(c, c->d_hh_tags, 0, ((size_t)4) << c->hh_log2, c->stream));
+  HIPCHK(c, x_set_async(c, c->d_hh_words, 0, kHhWords * 8, c->stream));
+  return GPUAGG_OK;
+}
+void hh_free(gpuagg_ctx *c) {
+  dev_free(c, c->d_hh_keys);
+  dev_free(c, c->d_hh_tags);
+  dev_free(c, c->d_hh_words);
+  c->hh_cpu = gpuagg::cpu::HhSet{};
+  c->hh_min = c->hh_log2 = 0;
+}
+
 int reset_state(gpuagg_ctx *c) {
   drop_pending(c);
   delta_drop(c);  // the next delta starts from zero again ("rebased")
@@ -823,6 +855,7 @@ int reset_state(gpuagg_ctx *c) {
   }
   if (c->cms_len) HIPCHK(c, x_set_async(c, c->d_cms, 0, c->cms_len * 4, c->stream));
   if (c->hll_len) HIPCHK(c, x_set_async(c, c->d_hll, 0, c->hll_len, c->stream));
+  if (int rc = hh_clear(c)) return rc;
   HIPCHK(c, x_sync(c, c->stream));
   return GPUAGG_OK;
 }
@@ -1290,6 +1323,23 @@ int fold_pending_sketch(gpuagg_ctx *c) {
   return GPUAGG_OK;
 }
 
+// The waiting count-min lists alone folded into the rows (the heavy-hitter test of a submit
+// reads them); the HLL lists stay deferred, and later scatters append to count-min lists
+// that start empty again.
+int hh_fold_cms(gpuagg_ctx *c) {
+  if (!c->sk_pend.active) return GPUAGG_OK;
+  SketchArgs s = c->sk_pend.s;
+  if (!s.nwin || !s.cms_depth) return GPUAGG_OK;  // count-min updates were direct atomics
+  if (!s.hll_nsup || !s.hll_p) return fold_pending_sketch(c);  // nothing of HLL waits
+  s.passes = kSketchFolds;
+  s.accum = false;
+  s.hll_nsup = 0;  // launch_sketch: no HLL split / fold
+  ENQ(c);
+  HIPCHK(c, launch_sketch(s, c->stream, nullptr));
+  HIPCHK(c, x_set_async(c, s.counts, 0, (size_t)s.blocks * s.nwin * 4, c->stream));
+  return GPUAGG_OK;
+}
+
 // The sketch pass over n records: count-min scatter + fold, HLL direct (SketchArgs).
 int launch_sketches(gpuagg_ctx *c, const ColsView &cv, size_t n) {
   int rc;
@@ -1311,6 +1361,7 @@ int launch_sketches(gpuagg_ctx *c, const ColsView &cv, size_t n) {
     s.cols = ColsView{cv.src_ip, cv.dst_ip, nullptr, cv.meta, cv.ports, nullptr};
     s.n = n;
     c->cpu->sketch(s);
+    if (c->hh_min) c->hh_cpu.pass(cv, n, c->d_cms, c->cfg.cms_depth, c->cfg.cms_width_log2, c->hh_min);
     return GPUAGG_OK;
   }
   if (s.hll_p && c->ipl_all_bytes) {
@@ -1456,6 +1507,19 @@ int launch_sketches(gpuagg_ctx *c, const ColsView &cv, size_t n) {
     if (c->timing && (rc = t_open(evf))) return rc;
     HIPCHK(c, launch_sketch(s, c->stream, nullptr));
     if (c->timing && (rc = t_close(evf, c->pending_fold))) return rc;
+  }
+  // heavy hitters: every record of this submit against the rows that now hold all of it
+  if (c->hh_min && n) {
+    if ((rc = hh_fold_cms(c))) return rc;
+    HhArgs h{};
+    h.table = hh_table(c);
+    h.cols = cv;
+    h.n = n;
+    h.blocks = c->n_cu;
+    h.chunk = ((n + h.blocks - 1) / h.blocks + 3) & ~3ULL;
+    h.min_count = c->hh_min;
+    ENQ(c);
+    HIPCHK(c, launch_hh_candidates(h, c->stream));
   }
   return GPUAGG_OK;
 }
@@ -2367,6 +2431,7 @@ void gpuagg_destroy(gpuagg_ctx *c) {
   if (c->ovf_event) hipEventDestroy(c->ovf_event);
   dev_free(c, c->d_export);
   delta_drop(c);
+  hh_free(c);
   dev_free(c, c->d_cms);
   dev_free(c, c->d_hll);
   dev_free(c, c->d_spill);
@@ -4813,6 +4878,244 @@ int gpuagg_hll_copy(gpuagg_ctx *c, uint8_t *out, size_t n) {
   return GPUAGG_OK;
 }
 
+// ---- sketch readouts: heavy hitters, distinct peers of every pod -------------------------
+namespace {
+// The candidates and the refused inserts, read from the device (a key that came to hold two
+// slots is marked and counted once: launch_hh_count).
+int hh_count(gpuagg_ctx *c, uint64_t *candidates, uint64_t *dropped) {
+  if (c->cpu) {
+    *candidates = c->hh_cpu.keys.size();
+    *dropped = c->hh_cpu.dropped;
+    return GPUAGG_OK;
+  }
+  uint64_t w[kHhWords];
+  ENQ(c);
+  HIPCHK(c, launch_hh_count(hh_table(c), c->stream));
+  HIPCHK(c, x_copy_async(c, w, c->d_hh_words, sizeof w, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, x_sync(c, c->stream));
+  *candidates = w[kHhWordCount];
+  *dropped = w[kHhWordDropped];
+  return GPUAGG_OK;
+}
+
+// Every candidate key (4 words each) on the host.
+int hh_collect(gpuagg_ctx *c, std::vector<uint32_t> &keys) {
+  keys.clear();
+  if (c->cpu) {
+    for (const auto &k : c->hh_cpu.keys) keys.insert(keys.end(), k.begin(), k.end());
+    return GPUAGG_OK;
+  }
+  uint64_t cand = 0, dropped = 0;
+  int rc = hh_count(c, &cand, &dropped);
+  if (rc || !cand) return rc;
+  uint32_t *d = nullptr;
+  if ((rc = dev_alloc(c, &d, (size_t)cand * 4))) return rc;
+  keys.resize((size_t)cand * 4);
+  ENQ(c);
+  hipError_t e = launch_hh_export(hh_table(c), d, (size_t)cand, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(keys.data(), d, keys.size() * 4, hipMemcpyDeviceToHost, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  dev_free(c, d);
+  if (e != hipSuccess) return fail(c, GPUAGG_EDEVICE, "heavy-hitter export: %s", hipGetErrorString(e));
+  return GPUAGG_OK;
+}
+
+int hh_add(gpuagg_ctx *c, const uint32_t *keys4, size_t n) {
+  if (!n) return GPUAGG_OK;
+  if (c->cpu) {
+    c->hh_cpu.add(keys4, n);
+    return GPUAGG_OK;
+  }
+  uint32_t *d = nullptr;
+  if (int rc = dev_alloc(c, &d, n * 4)) return rc;
+  ENQ(c);
+  hipError_t e = hipMemcpyAsync(d, keys4, n * 16, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = launch_hh_add(hh_table(c), d, n, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  dev_free(c, d);
+  if (e != hipSuccess) return fail(c, GPUAGG_EDEVICE, "heavy-hitter insert: %s", hipGetErrorString(e));
+  return GPUAGG_OK;
+}
+
+bool hh_entry_before(const HhEntry &a, const HhEntry &b) {
+  if (a.estimate != b.estimate) return a.estimate > b.estimate;
+  if (a.src_ip != b.src_ip) return a.src_ip < b.src_ip;
+  if (a.dst_ip != b.dst_ip) return a.dst_ip < b.dst_ip;
+  if (a.ports != b.ports) return a.ports < b.ports;
+  return a.proto < b.proto;
+}
+static_assert(sizeof(HhEntry) == sizeof(gpuagg_hh_entry) && sizeof(HhEntry) == 24, "gpuagg_hh_entry layout");
+}  // namespace
+
+int gpuagg_set_heavy_hitters(gpuagg_ctx *c, uint32_t min_count, uint32_t capacity_log2) {
+  if (!c) return GPUAGG_EINVAL;
+  int rc = bind(c);
+  if (rc) return rc;
+  if (!min_count) {  // off: the table goes
+    HIPCHK(c, x_sync(c, c->stream));
+    hh_free(c);
+    return GPUAGG_OK;
+  }
+  if (!c->cms_len) return fail(c, GPUAGG_ESTATE, "heavy hitters need the count-min sketch (cms_depth != 0)");
+  if (!capacity_log2) capacity_log2 = 16;
+  if (capacity_log2 < 4 || capacity_log2 > 24)
+    return fail(c, GPUAGG_EINVAL, "heavy hitters: capacity_log2 %u outside [4, 24]", capacity_log2);
+  if (min_count == c->hh_min && capacity_log2 == c->hh_log2) return GPUAGG_OK;
+  HIPCHK(c, x_sync(c, c->stream));  // in-flight candidate passes use the old table
+  hh_free(c);
+  const size_t slots = (size_t)1 << capacity_log2;
+  if (c->cpu) {
+    c->hh_cpu.capacity = slots;
+  } else if ((rc = dev_alloc(c, &c->d_hh_keys, slots)) || (rc = dev_alloc(c, &c->d_hh_tags, slots)) ||
+             (rc = dev_alloc(c, &c->d_hh_words, kHhWords))) {
+    hh_free(c);
+    return rc;
+  }
+  c->hh_min = min_count;
+  c->hh_log2 = capacity_log2;
+  if ((rc = hh_clear(c))) return rc;
+  if (!c->cpu) HIPCHK(c, x_set_async(c, c->d_hh_keys, 0, slots * sizeof(uint4), c->stream));
+  HIPCHK(c, x_sync(c, c->stream));
+  return GPUAGG_OK;
+}
+
+int gpuagg_hh_info(gpuagg_ctx *c, uint64_t *candidates, uint64_t *dropped, uint32_t *min_count,
+                   uint32_t *capacity_log2) {
+  if (!c) return GPUAGG_EINVAL;
+  int rc = bind(c);
+  if (rc) return rc;
+  uint64_t cand = 0, drop = 0;
+  if (c->hh_min && (candidates || dropped) && (rc = hh_count(c, &cand, &drop))) return rc;
+  if (candidates) *candidates = cand;
+  if (dropped) *dropped = drop;
+  if (min_count) *min_count = c->hh_min;
+  if (capacity_log2) *capacity_log2 = c->hh_log2;
+  return GPUAGG_OK;
+}
+
+int gpuagg_heavy_hitters(gpuagg_ctx *c, gpuagg_hh_entry *out, size_t k, size_t *n) {
+  if (!c || !n || (k && !out)) return GPUAGG_EINVAL;
+  *n = 0;
+  if (!c->hh_min) return fail(c, GPUAGG_ESTATE, "heavy hitters are off (gpuagg_set_heavy_hitters)");
+  int rc = bind(c);
+  if (rc) return rc;
+  if ((rc = fold_pending(c))) return rc;
+  std::vector<HhEntry> top;
+  if (c->cpu) {
+    c->hh_cpu.top(c->d_cms, c->cfg.cms_depth, c->cfg.cms_width_log2, k, top);
+  } else {
+    uint64_t cand = 0, dropped = 0;
+    if ((rc = hh_count(c, &cand, &dropped))) return rc;
+    const size_t kk = (size_t)std::min<uint64_t>(k, cand);
+    if (!kk) return GPUAGG_OK;
+    // the ranking's buffers live for this call only: 16 bytes per slot and rocprim's scratch
+    const size_t slots = (size_t)1 << c->hh_log2;
+    size_t tmp_bytes = 0;
+    HIPCHK(c, hh_sort_bytes(slots, &tmp_bytes));
+    uint64_t *sort = nullptr;
+    uint8_t *tmp = nullptr;
+    HhEntry *ent = nullptr;
+    auto cleanup = [&] {
+      dev_free(c, sort);
+      dev_free(c, tmp);
+      dev_free(c, ent);
+    };
+    if ((rc = dev_alloc(c, &sort, 2 * slots)) || (rc = dev_alloc(c, &tmp, std::max<size_t>(tmp_bytes, 16)))) {
+      cleanup();
+      return rc;
+    }
+    uint64_t m = 0;
+    ENQ(c);
+    hipError_t e = launch_hh_rank(hh_table(c), sort, sort + slots, tmp, tmp_bytes, kk, c->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(&m, c->d_hh_words + kHhWordSelect, 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && (m < kk || m > cand)) {
+      cleanup();
+      return fail(c, GPUAGG_EDEVICE, "heavy-hitter ranking selected %llu of %llu candidates for k = %zu",
+                  (unsigned long long)m, (unsigned long long)cand, kk);
+    }
+    if (e == hipSuccess && (rc = dev_alloc(c, &ent, (size_t)m))) {
+      cleanup();
+      return rc;
+    }
+    top.resize((size_t)m);
+    if (e == hipSuccess) e = launch_hh_gather(hh_table(c), sort + slots, (size_t)m, ent, c->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(top.data(), ent, (size_t)m * sizeof(HhEntry), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    cleanup();
+    if (e != hipSuccess) return fail(c, GPUAGG_EDEVICE, "heavy-hitter ranking: %s", hipGetErrorString(e));
+    // the device ordered by estimate; the order among equal estimates is the host's
+    std::sort(top.begin(), top.end(), hh_entry_before);
+    top.resize(kk);
+  }
+  if (!top.empty()) memcpy(out, top.data(), top.size() * sizeof(HhEntry));
+  *n = top.size();
+  return GPUAGG_OK;
+}
+
+int gpuagg_hh_candidates(gpuagg_ctx *c, uint32_t *keys4, size_t cap, size_t *n) {
+  if (!c || !n || (cap && !keys4)) return GPUAGG_EINVAL;
+  *n = 0;
+  if (!c->hh_min) return fail(c, GPUAGG_ESTATE, "heavy hitters are off (gpuagg_set_heavy_hitters)");
+  int rc = bind(c);
+  if (rc) return rc;
+  uint64_t cand = 0, dropped = 0;
+  if ((rc = hh_count(c, &cand, &dropped))) return rc;
+  *n = (size_t)cand;
+  if (cap < cand) return fail(c, GPUAGG_ECAPACITY, "%llu candidates, room for %zu", (unsigned long long)cand, cap);
+  std::vector<uint32_t> keys;
+  if ((rc = hh_collect(c, keys))) return rc;
+  if (!keys.empty()) memcpy(keys4, keys.data(), keys.size() * 4);
+  return GPUAGG_OK;
+}
+
+int gpuagg_hh_add_candidates(gpuagg_ctx *c, const uint32_t *keys4, size_t n) {
+  if (!c || (n && !keys4)) return GPUAGG_EINVAL;
+  if (!c->hh_min) return fail(c, GPUAGG_ESTATE, "heavy hitters are off (gpuagg_set_heavy_hitters)");
+  int rc = bind(c);
+  if (rc) return rc;
+  return hh_add(c, keys4, n);
+}
+
+int gpuagg_hll_estimate_all(gpuagg_ctx *c, double *out, size_t cap, size_t *n) {
+  if (!c || !n || (cap && !out)) return GPUAGG_EINVAL;
+  *n = 0;
+  if (!c->hll_len) return fail(c, GPUAGG_ESTATE, "no HLL sketch (hll_precision == 0)");
+  const uint32_t p = c->cfg.hll_precision;
+  const size_t rows = c->hll_len >> p;
+  *n = rows;
+  if (cap < rows) return fail(c, GPUAGG_ECAPACITY, "%zu HLL rows, room for %zu", rows, cap);
+  int rc = bind(c);
+  if (rc) return rc;
+  if ((rc = fold_pending(c))) return rc;
+  std::vector<uint64_t> sums(rows * 3);
+  if (c->cpu) {
+    cpu::hll_sums(c->d_hll, p, (uint32_t)rows, sums.data());
+  } else {
+    uint64_t *d = nullptr;
+    if ((rc = dev_alloc(c, &d, rows * 3))) return rc;
+    ENQ(c);
+    hipError_t e = launch_hll_estimate(c->d_hll, p, (uint32_t)rows, d, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(sums.data(), d, rows * 24, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    dev_free(c, d);
+    if (e != hipSuccess) return fail(c, GPUAGG_EDEVICE, "hll_estimate_kernel: %s", hipGetErrorString(e));
+  }
+  // gpuagg_hll_estimate's estimator on the exact sums: sum 2^-r = lo / 2^32 + hi / 2^64
+  const double md = std::ldexp(1.0, (int)p);
+  const double alpha = 0.7213 / (1.0 + 1.079 / md);
+  for (size_t s = 0; s < rows; ++s) {
+    const uint64_t zeros = sums[3 * s];
+    const double sum = std::ldexp((double)sums[3 * s + 1], -32) + std::ldexp((double)sums[3 * s + 2], -64);
+    double e = alpha * md * md / sum;
+    if (e <= 2.5 * md && zeros) e = md * std::log(md / (double)zeros);  // linear counting
+    out[s] = e;
+  }
+  return GPUAGG_OK;
+}
+
 // ---- multi-GPU merge hooks -----------------------------------------------------------
 int gpuagg_state(gpuagg_ctx *c, gpuagg_state_desc *o) {
   if (!c || !o) return GPUAGG_EINVAL;
@@ -5056,6 +5359,9 @@ int gpuagg_merge(gpuagg_ctx *const *ctxs, size_t n) {
              ci->dns[k].ips == c0->dns[k].ips;
     if (!same)
       return fail(c0, GPUAGG_EINVAL, "merge: ctx %zu has another metric plan or slot/DNS dictionary", i);
+    if (ci->hh_min != c0->hh_min)
+      return fail(c0, GPUAGG_EINVAL, "merge: ctx %zu has heavy-hitter min_count %u, the target %u", i, ci->hh_min,
+                  c0->hh_min);
     cap = std::max<size_t>(cap, ci->key_cap);
   }
   // one layout everywhere (the largest slot coverage), then every stream idle
@@ -5067,6 +5373,16 @@ int gpuagg_merge(gpuagg_ctx *const *ctxs, size_t n) {
     if (ci->key_cap < cap && (rc = layout_dense(ci, (uint32_t)cap, true))) return rc;
     HIPCHK(ci, x_sync(ci, ci->stream));
     HIPCHK(ci, x_sync(ci, ci->copy_stream));
+  }
+  // heavy-hitter candidates: the union (records are sharded by 5-tuple, so a flow's count
+  // lives on one ctx and its estimate in the summed rows is at least that); the keys go
+  // through the host, 16 bytes each
+  if (c0->hh_min) {
+    std::vector<uint32_t> keys;
+    for (size_t i = 1; i < n; ++i) {
+      if ((rc = bind(ctxs[i])) || (rc = hh_collect(ctxs[i], keys))) return rc;
+      if ((rc = bind(c0)) || (rc = hh_add(c0, keys.data(), keys.size() / 4))) return rc;
+    }
   }
   if ((rc = bind(c0))) return rc;
   // distinct devices: the RCCL collectives over xGMI (merge_rccl); contexts sharing a

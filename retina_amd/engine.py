@@ -500,6 +500,53 @@ class GpuAgg:
         self._check(self.lib.gpuagg_hll_copy(self.h, a.ctypes.data_as(C.POINTER(C.c_uint8)), a.size))
         return a.reshape(-1, 1 << self.cfg.hll_precision) if a.size else a
 
+    # -- sketch readouts -------------------------------------------------------------------
+    def set_heavy_hitters(self, min_count: int, capacity_log2: int = 0) -> None:
+        """gpuagg_set_heavy_hitters: from the next submit on, every key whose count-min estimate
+        reaches min_count becomes a candidate (min_count 0: off, the table is freed)."""
+        self._check(self.lib.gpuagg_set_heavy_hitters(self.h, min_count, capacity_log2))
+
+    def hh_info(self) -> Dict[str, int]:
+        cand, dropped, mc, lg = C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint32()
+        self._check(self.lib.gpuagg_hh_info(self.h, C.byref(cand), C.byref(dropped), C.byref(mc), C.byref(lg)))
+        return {"candidates": cand.value, "dropped": dropped.value, "min_count": mc.value,
+                "capacity_log2": lg.value}
+
+    def heavy_hitters(self, k: int) -> np.ndarray:
+        """The k candidates with the largest current estimate, as a structured array
+        (_abi.HH_ENTRY), estimate descending, then key ascending."""
+        out = np.zeros(max(k, 1), _abi.HH_ENTRY)
+        n = C.c_size_t()
+        self._check(self.lib.gpuagg_heavy_hitters(self.h, out.ctypes.data_as(C.c_void_p), k, C.byref(n)))
+        return out[:n.value]
+
+    def hh_candidates(self) -> np.ndarray:
+        """Every candidate key, uint32 [n, 4] (src_ip, dst_ip, ports, proto), in any order."""
+        n = C.c_size_t()
+        rc = self.lib.gpuagg_hh_candidates(self.h, None, 0, C.byref(n))
+        if rc not in (_abi.OK, _abi.ECAPACITY):
+            self._check(rc)
+        out = np.zeros((n.value, 4), np.uint32)
+        if n.value:
+            self._check(self.lib.gpuagg_hh_candidates(self.h, out.ctypes.data_as(_abi.u32p), n.value, C.byref(n)))
+        return out[:n.value]
+
+    def hh_add_candidates(self, keys) -> None:
+        keys = np.ascontiguousarray(keys, np.uint32).reshape(-1, 4)
+        self._check(self.lib.gpuagg_hh_add_candidates(self.h, keys.ctypes.data_as(_abi.u32p), len(keys)))
+
+    def hll_estimates(self) -> np.ndarray:
+        """gpuagg_hll_estimate_all: the distinct-peer estimate of every HLL row, float64."""
+        n = C.c_size_t()
+        rc = self.lib.gpuagg_hll_estimate_all(self.h, None, 0, C.byref(n))
+        if rc not in (_abi.OK, _abi.ECAPACITY):
+            self._check(rc)
+        out = np.zeros(n.value, np.float64)
+        if n.value:
+            self._check(self.lib.gpuagg_hll_estimate_all(self.h, out.ctypes.data_as(C.POINTER(C.c_double)),
+                                                         n.value, C.byref(n)))
+        return out[:n.value]
+
     # -- merge / introspection -----------------------------------------------------------
     def state(self) -> "_abi.StateDesc":
         d = _abi.StateDesc()
