@@ -249,7 +249,7 @@ void Engine::aggregate(const LaunchArgs &a) {
   if (parts_.size() < threads_) parts_.resize(threads_);
   for (auto &p : parts_)
     if (!p) p.reset(new Part());
-  const IpTable t{a.ip_slots, a.ip_mask, a.ip_seed, a.ip_pre, a.ip_blk};
+  const IpTable t{a.ip.slots, a.ip.mask, a.ip.seed, a.ip.pre, a.ip.blk};
   dense_len_ = a.dense_len;
   dense_cnt_ = a.dense_cnt;
   dense_byt_ = a.dense_byt;
@@ -313,7 +313,7 @@ void Engine::drop() {
 
 // sketch_update of gpuagg_kernels.hip: count-min +1 per row, HLL register max.
 void Engine::sketch(const SketchArgs &s) {
-  const IpTable t{s.ip_slots, s.ip_mask, s.ip_seed, s.ip_pre, s.ip_blk};
+  const IpTable t{s.ip.slots, s.ip.mask, s.ip.seed, s.ip.pre, s.ip.blk};
   const uint32_t wmask = (1u << s.cms_wlog2) - 1u;
   parallel(threads_, s.n, [&](unsigned, size_t lo, size_t hi) {
     for (size_t i = lo; i < hi; ++i) {
@@ -366,7 +366,7 @@ uint64_t Engine::decode(const DecodeArgs &a) {
 
 // enrich_kernel of gpuagg_kernels.hip.
 void Engine::enrich(const EnrichArgs &a) {
-  const IpTable t{a.ip_slots, a.ip_mask, a.ip_seed, a.ip_pre, a.ip_blk};
+  const IpTable t{a.ip.slots, a.ip.mask, a.ip.seed, a.ip.pre, a.ip.blk};
   parallel(threads_, a.n, [&](unsigned, size_t lo, size_t hi) {
     for (size_t i = lo; i < hi; ++i) {
       a.o_src[i] = t.lookup(a.src[i]).slot;

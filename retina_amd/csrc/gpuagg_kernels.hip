@@ -2759,7 +2759,7 @@ hipError_t launch_sketch(const SketchArgs &a, hipStream_t st, std::string *kerne
   k.meta = a.cols.meta;
   k.n = a.n;
   k.chunk = a.chunk;
-  k.t = DevIpTable{a.ip_slots, a.ip_mask, a.ip_seed, a.ip_pre, a.ip_blk, 0u, {}};
+  k.t = DevIpTable{a.ip.slots, a.ip.mask, a.ip.seed, a.ip.pre, a.ip.blk, 0u, {}};
   k.cms = a.cms;
   k.depth = a.cms_depth;
   k.wlog2 = a.cms_wlog2;
@@ -2786,14 +2786,14 @@ hipError_t launch_sketch(const SketchArgs &a, hipStream_t st, std::string *kerne
   hipError_t e;
   size_t scatter_lds = (size_t)((a.nwin + a.hll_nsup + 3u) & ~3u) * 4;
   // source lookups in an LDS image of the IP table when it fits next to the counters
-  const bool lds_ip_any = a.ipl && a.hll_p && scatter_lds + a.ipl_bytes <= kLdsBytes;
+  const bool lds_ip_any = a.ipl.p && a.hll_p && scatter_lds + a.ipl.bytes <= kLdsBytes;
   const bool lds_ip = lds_ip_any;  // (staged kernel: either image form)
   if (lds_ip) {
-    k.ipl = a.ipl;
-    k.ipl_nb = a.ipl_nb;
-    k.ipl_seed = a.ipl_seed;
-    k.ipl_bytes = a.ipl_bytes;
-    scatter_lds += a.ipl_bytes;
+    k.ipl = a.ipl.p;
+    k.ipl_nb = a.ipl.nb;
+    k.ipl_seed = a.ipl.seed;
+    k.ipl_bytes = a.ipl.bytes;
+    scatter_lds += a.ipl.bytes;
   }
   // 16-byte loads need aligned columns and workgroup chunks of whole vectors
   const bool vec = a.chunk % 4 == 0 && ((uintptr_t)k.src | (uintptr_t)k.dst | (uintptr_t)k.meta |
@@ -2806,15 +2806,15 @@ hipError_t launch_sketch(const SketchArgs &a, hipStream_t st, std::string *kerne
   bool staged = !scatter;  // a fold-only call launches no scatter
   if (scatter && vec && a.cms_depth <= (uint32_t)kStageMaxDepth && (!a.cms_depth || a.nwin) &&
       (!a.hll_p || a.hll_nsup) && (a.nwin || a.hll_nsup)) {
-    const int ip_kind = lds_ip ? (a.ipl_dense ? 3 : a.ipl_radix ? 2 : 1) : 0;
+    const int ip_kind = lds_ip ? (a.ipl.dense ? 3 : a.ipl.radix ? 2 : 1) : 0;
     if (lds_ip) {
-      k.ipl_npfx = a.ipl_npfx;
+      k.ipl_npfx = a.ipl.npfx;
       for (uint32_t j = 0; j < kIprMaxPfx; ++j) {
-        k.ipl_pfx[j] = a.ipl_pfx[j];
-        k.ipl_dr[j] = a.ipl_dr[j];
+        k.ipl_pfx[j] = a.ipl.pfx[j];
+        k.ipl_dr[j] = a.ipl.dr[j];
       }
     }
-    const uint32_t img = lds_ip ? a.ipl_bytes : 0u;
+    const uint32_t img = lds_ip ? a.ipl.bytes : 0u;
     for (uint32_t round : {4u, 2u}) {
       const uint64_t per_round = 1024ull * round;
       auto ring = [](uint64_t mean) {
@@ -2851,7 +2851,7 @@ hipError_t launch_sketch(const SketchArgs &a, hipStream_t st, std::string *kerne
   }
   if (!staged) {
   // the unstaged kernel probes the cuckoo image only: a radix image is looked up in HBM
-  const bool lds_ip = lds_ip_any && !a.ipl_radix && !a.ipl_dense;
+  const bool lds_ip = lds_ip_any && !a.ipl.radix && !a.ipl.dense;
   if (!lds_ip) scatter_lds = (size_t)((a.nwin + a.hll_nsup + 3u) & ~3u) * 4;
   const void *fn = vec ? (lds_ip ? (const void *)sketch_scatter_kernel<true, true>
                                  : (const void *)sketch_scatter_kernel<true, false>)
@@ -3518,11 +3518,11 @@ static hipError_t launch_k(K kern, const KArgs &k, uint32_t blocks, uint32_t thr
 template <int NG, uint32_t SIG>
 static hipError_t launch_lds(const LaunchArgs &a, const KArgs &k, uint32_t B, uint32_t T, size_t lds, hipStream_t st) {
   if (a.vec)
-    return a.ipl_dense   ? launch_k(dense_lds_kernel<NG, true, SIG, 2>, k, B, T, lds, st)
-           : a.ipl_radix ? launch_k(dense_lds_kernel<NG, true, SIG, 1>, k, B, T, lds, st)
+    return a.ipl.dense   ? launch_k(dense_lds_kernel<NG, true, SIG, 2>, k, B, T, lds, st)
+           : a.ipl.radix ? launch_k(dense_lds_kernel<NG, true, SIG, 1>, k, B, T, lds, st)
                          : launch_k(dense_lds_kernel<NG, true, SIG, 0>, k, B, T, lds, st);
-  return a.ipl_dense   ? launch_k(dense_lds_kernel<NG, false, SIG, 2>, k, B, T, lds, st)
-         : a.ipl_radix ? launch_k(dense_lds_kernel<NG, false, SIG, 1>, k, B, T, lds, st)
+  return a.ipl.dense   ? launch_k(dense_lds_kernel<NG, false, SIG, 2>, k, B, T, lds, st)
+         : a.ipl.radix ? launch_k(dense_lds_kernel<NG, false, SIG, 1>, k, B, T, lds, st)
                        : launch_k(dense_lds_kernel<NG, false, SIG, 0>, k, B, T, lds, st);
 }
 
@@ -3532,7 +3532,7 @@ hipError_t launch_aggregate(const LaunchArgs &a, hipStream_t st, hipEvent_t betw
   k.c = DevCols{a.cols.src_ip, a.cols.dst_ip, a.cols.bytes, a.cols.meta, a.cols.ports, a.cols.dns_id};
   k.n = a.n;
   k.chunk = a.chunk;
-  k.t = DevIpTable{a.ip_slots, a.ip_mask, a.ip_seed, a.ip_pre, a.ip_blk, a.ip_rpn, {}};
+  k.t = DevIpTable{a.ip.slots, a.ip.mask, a.ip.seed, a.ip.pre, a.ip.blk, a.ip_rpn, {}};
   for (uint32_t j = 0; j < kRadixSmall / 2; ++j) k.t.rp[j] = a.ip_rp[j];
   k.d = DevDense{(unsigned long long *)a.dense_cnt, (unsigned long long *)a.dense_byt};
   k.s = dev_sparse(a.sparse);
@@ -3544,14 +3544,14 @@ hipError_t launch_aggregate(const LaunchArgs &a, hipStream_t st, hipEvent_t betw
   k.win_shift = a.win_shift;
   k.spill_lo = a.spill_lo;
   k.spill_count = a.spill_count;
-  k.ipl = a.ipl;
-  k.ipl_nb = a.ipl_nb;
-  k.ipl_seed = a.ipl_seed;
-  k.ipl_bytes = a.ipl_bytes;
-  k.ipl_npfx = a.ipl_npfx;
+  k.ipl = a.ipl.p;
+  k.ipl_nb = a.ipl.nb;
+  k.ipl_seed = a.ipl.seed;
+  k.ipl_bytes = a.ipl.bytes;
+  k.ipl_npfx = a.ipl.npfx;
   for (uint32_t j = 0; j < kIprMaxPfx; ++j) {
-    k.ipl_pfx[j] = a.ipl_pfx[j];
-    k.ipl_dr[j] = a.ipl_dr[j];
+    k.ipl_pfx[j] = a.ipl.pfx[j];
+    k.ipl_dr[j] = a.ipl.dr[j];
   }
   k.stage_a = a.stage_a;
   k.stage_a_stride = a.stage_a_stride;
@@ -3572,7 +3572,7 @@ hipError_t launch_aggregate(const LaunchArgs &a, hipStream_t st, hipEvent_t betw
   k.fold_parity = a.fold_parity;
   k.p = a.plan;
   const bool sketch = a.cms_depth || a.hll_p;
-  size_t lds = a.tier1 ? (size_t)a.ipl_bytes + (size_t)a.lds_bins * 4 + kL4ExtraBytes
+  size_t lds = a.tier1 ? (size_t)a.ipl.bytes + (size_t)a.lds_bins * 4 + kL4ExtraBytes
                        : ((size_t)a.lds_bins + kLdsExtraWords) * 8 + (size_t)k.sp_nwin * 4 +
                              (a.hot_n ? 4 + (size_t)a.hot_n * kHotKeyBytes : 0);
   // the hot-key cache's doorkeeper bitmap takes what LDS is left (2^13 .. 2^18 bits) on the
@@ -3601,14 +3601,14 @@ hipError_t launch_aggregate(const LaunchArgs &a, hipStream_t st, hipEvent_t betw
     // LDS: (remote context) the image of every pod IP when it fits next to a cache of
     // >= kWideIplMinHot entries and a 2^kWideIplMinDoor-bit doorkeeper (the cache halves
     // until it does), counters, cache, then the largest doorkeeper bitmap that fits
-    const size_t ctr = (size_t)((k.sp_nwin + 1) / 2) * 8, img = remote && a.ipl ? ((size_t)a.ipl_bytes + 15) & ~15ull : 0;
+    const size_t ctr = (size_t)((k.sp_nwin + 1) / 2) * 8, img = remote && a.ipl.p ? ((size_t)a.ipl.bytes + 15) & ~15ull : 0;
     int kip = -1;
     if (img) {
       uint32_t hn = k.hot_n;
       while (hn > kWideIplMinHot && img + ctr + (size_t)hn * kHotKeyBytes + ((size_t)1 << (kWideIplMinDoor - 3)) > kLdsBytes)
         hn >>= 1;
       if (img + ctr + (size_t)hn * kHotKeyBytes + ((size_t)1 << (kWideIplMinDoor - 3)) <= kLdsBytes) {
-        kip = a.ipl_dense ? 2 : a.ipl_radix ? 1 : 0;
+        kip = a.ipl.dense ? 2 : a.ipl.radix ? 1 : 0;
         k.hot_n = hn;
       }
     }
@@ -3670,14 +3670,14 @@ hipError_t launch_aggregate(const LaunchArgs &a, hipStream_t st, hipEvent_t betw
   static const bool trace = getenv("GPUAGG_TRACE") != nullptr;
   if (trace)
     fprintf(stderr, "gpuagg: launch variant=%d tier1=%d sig=0x%x ng=%u L=%u ipl_bytes=%u nwin=%u n=%llu\n",
-            variant, (int)a.tier1, a.sig, a.dense_ng, a.lds_bins, a.ipl_bytes, a.nwin,
+            variant, (int)a.tier1, a.sig, a.dense_ng, a.lds_bins, a.ipl.bytes, a.nwin,
             (unsigned long long)a.n);
   if (kernel) {
     static thread_local char name[64];
     if (a.tier1)
       snprintf(name, sizeof name, "dense_lds_kernel<%u, %s, %uu, %d>",
                variant >= 200 ? (variant == 202 ? 1u : 2u) : a.dense_ng, a.vec ? "true" : "false",
-               variant >= 200 ? a.sig : 0u, a.ipl_dense ? 2 : a.ipl_radix ? 1 : 0);
+               variant >= 200 ? a.sig : 0u, a.ipl.dense ? 2 : a.ipl.radix ? 1 : 0);
     else if (a.dense_ng)
       snprintf(name, sizeof name, "dense_local_kernel<%u, %s, %s, %uu%s>", a.dense_ng, a.vec ? "true" : "false",
                a.dns_compact ? "true" : "false", variant == 305 || variant == 306 ? a.sig : 0u,
@@ -3882,7 +3882,7 @@ hipError_t launch_enrich(const EnrichArgs &a, uint32_t n_cu, hipStream_t st) {
   const uint64_t need = (lanes + 255) / 256;
   const uint32_t blocks = (uint32_t)(need < (uint64_t)n_cu * 8 ? need : (uint64_t)n_cu * 8);
   hipLaunchKernelGGL(enrich_kernel, dim3(blocks), dim3(256), 0, st,
-                     DevIpTable{a.ip_slots, a.ip_mask, a.ip_seed, a.ip_pre, a.ip_blk, 0u, {}}, a.src, a.dst,
+                     DevIpTable{a.ip.slots, a.ip.mask, a.ip.seed, a.ip.pre, a.ip.blk, 0u, {}}, a.src, a.dst,
                      (uint64_t)a.n, a.o_src, a.o_dst, vec);
   return hipGetLastError();
 }

@@ -33,14 +33,27 @@ struct SparseView {
   uint64_t *overflow = nullptr;
 };
 
+// The IP -> slot table in HBM: buckets of two entries, and the radix form when the IPs allow one.
+struct IpTableView {
+  const uint64_t *slots;
+  uint32_t mask, seed;  // bucket mask
+  const uint16_t *pre;  // radix IP table (null: the bucket table above)
+  const uint32_t *blk;
+};
+
+// An LDS image of an IP table (ipl_build.h) in device memory; bytes 0: none.
+struct IpImage {
+  const uint8_t *p;
+  uint32_t nb, seed, bytes;
+  bool radix;  // radix image (ipr_build): prefixes below, no nb / seed
+  bool dense;  // dense radix image (iprd_build): prefixes + descriptors
+  uint32_t npfx, pfx[kIprMaxPfx], dr[kIprMaxPfx];
+};
+
 struct LaunchArgs {
   ColsView cols;
   size_t n;
-  const uint64_t *ip_slots;
-  uint32_t ip_mask;
-  uint32_t ip_seed;
-  const uint16_t *ip_pre;  // radix IP table (null: the bucket table above)
-  const uint32_t *ip_blk;
+  IpTableView ip;
   uint32_t ip_rpn;                       // radix prefixes resolved by compares (0: use ip_pre)
   uint32_t ip_rp[kRadixSmall / 2];
   Plan plan;
@@ -65,11 +78,7 @@ struct LaunchArgs {
   bool dns_compact;     // dense kernel also inserts the compact plan's DNS keys (segment lists)
   bool tier1;           // dense kernel with the IP table and u32 bins in LDS
   uint32_t sig;         // tier-1 group signature (kSig*), 0 when the plan has none
-  const uint8_t *ipl;
-  uint32_t ipl_nb, ipl_seed, ipl_bytes;
-  bool ipl_radix;                   // radix image (ipr_build): prefixes below, no nb / seed
-  bool ipl_dense;                   // dense radix image (iprd_build): prefixes + descriptors
-  uint32_t ipl_npfx, ipl_pfx[kIprMaxPfx], ipl_dr[kIprMaxPfx];
+  IpImage ipl;          // tier-1: the local pods; wide_kernel (remote context): every pod
   // staged flushes (null: flush with global atomics)
   uint32_t *stage_a;        // tier-1: [blocks][stage_a_stride] copies of the u32 LDS bins
   uint32_t stage_a_stride;
@@ -127,10 +136,7 @@ hipError_t launch_decode(const DecodeArgs &a, hipStream_t st);
 
 // Standard-mode enriched-flow emission (enrich_kernel, gpuagg_kernels.hip).
 struct EnrichArgs {
-  const uint64_t *ip_slots;
-  uint32_t ip_mask, ip_seed;
-  const uint16_t *ip_pre;
-  const uint32_t *ip_blk;
+  IpTableView ip;
   const uint32_t *src, *dst;
   size_t n;
   int32_t *o_src, *o_dst;
@@ -238,10 +244,7 @@ struct SketchArgs {
   size_t n;
   uint64_t chunk;           // records per scatter workgroup
   uint32_t blocks;          // scatter workgroups (= lists per window)
-  const uint64_t *ip_slots;
-  uint32_t ip_mask, ip_seed;
-  const uint16_t *ip_pre;  // radix IP table (null: the bucket table above)
-  const uint32_t *ip_blk;
+  IpTableView ip;
   uint32_t *cms;
   uint32_t cms_depth, cms_wlog2;
   uint32_t win_shift, nwin, cap;  // windows of 2^win_shift columns; nwin 0: direct atomics
@@ -257,11 +260,7 @@ struct SketchArgs {
   uint32_t *hll_lists, *hll_counts;
   uint32_t hll_b2, hll_cap2;
   uint32_t *hll_lists2, *hll_counts2;
-  const uint8_t *ipl;               // LDS image of every pod IP for the source lookup, or null
-  uint32_t ipl_nb, ipl_seed, ipl_bytes;
-  bool ipl_radix;                   // the image is the radix form (ipl_npfx / ipl_pfx)
-  bool ipl_dense;                   // ... the dense radix form (ipl_pfx / ipl_dr)
-  uint32_t ipl_npfx, ipl_pfx[kIprMaxPfx], ipl_dr[kIprMaxPfx];
+  IpImage ipl;                      // LDS image of every pod IP for the source lookup (bytes 0: none)
   // which kernels run: the scatter, the folds, or both (kSketchBoth, the default 0); a
   // scatter with accum appends after the fill earlier scatters stored (deferred folds)
   uint32_t passes;

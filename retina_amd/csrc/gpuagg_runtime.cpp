@@ -228,6 +228,76 @@ struct ScrapePool {
   size_t text_cap = 0;
 };
 
+// ---- owners of the ctx's device resources --------------------------------------------------
+// Each frees what it holds when it goes out of scope (a ctx member: at `delete c`) and reads
+// as the plain pointer / event it owns, so the launch interface keeps taking views.
+
+// A device buffer of `cap` elements -- CPU backend: 64-byte aligned, zeroed host memory.
+template <class T>
+struct DevBuf {
+  T *p = nullptr;
+  size_t cap = 0;
+  bool host = false;  // from aligned_alloc (CPU backend), not hipMalloc
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap), host(o.host) { o.p = nullptr, o.cap = 0; }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    std::swap(p, o.p), std::swap(cap, o.cap), std::swap(host, o.host);
+    o.reset();
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  operator T *() const { return p; }
+  void reset() {
+    if (p) host ? free((void *)p) : (void)hipFree((void *)p);
+    p = nullptr;
+    cap = 0;
+  }
+  // Frees what it holds, then allocates `count` elements (0: none); on failure it is empty.
+  int alloc(gpuagg_ctx *c, size_t count);
+  // Grows a lazily allocated buffer to at least `count` elements, contents not kept.
+  int ensure(gpuagg_ctx *c, size_t count);
+};
+
+// Pinned host memory (CPU backend: plain, zeroed), allocated once.
+template <class T>
+struct HostBuf {
+  T *p = nullptr;
+  bool pinned = false;
+  HostBuf() = default;
+  HostBuf(const HostBuf &) = delete;
+  HostBuf &operator=(const HostBuf &) = delete;
+  ~HostBuf() {
+    if (p) pinned ? (void)hipHostFree(p) : free(p);
+  }
+  operator T *() const { return p; }
+  int ensure(gpuagg_ctx *c, size_t count);
+};
+
+struct Event {
+  hipEvent_t e = nullptr;
+  Event() = default;
+  Event(const Event &) = delete;
+  Event &operator=(const Event &) = delete;
+  ~Event() {
+    if (e) (void)hipEventDestroy(e);
+  }
+  operator hipEvent_t() const { return e; }
+  hipError_t create(unsigned flags) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+};
+
+// A timed span on the stream: start and end events until span_close hands them to a list.
+struct Span {
+  std::array<hipEvent_t, 2> ev{};
+  Span() = default;
+  Span(const Span &) = delete;
+  Span &operator=(const Span &) = delete;
+  ~Span() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+using SpanList = std::vector<std::array<hipEvent_t, 2>>;
+
 }  // namespace
 
 struct gpuagg_result {
@@ -262,7 +332,11 @@ struct gpuagg_ctx {
   // (one per device of the merge, created once per device list)
   std::vector<int> rccl_devs;
   std::vector<ncclComm_t> rccl_comms;
+  // the streams come before every buffer and event below, which are so destroyed first
   hipStream_t stream = nullptr;
+  hipStream_t copy_stream = nullptr;
+  // deferred folds: the spill-window fold beside the segment fold (launch_folds' ForkJoin)
+  hipStream_t fold_stream = nullptr;
   std::string err;
 
   // registry / plan
@@ -314,50 +388,45 @@ struct gpuagg_ctx {
   uint64_t slots_version = 0;
 
   // IP table
-  uint64_t *d_ip = nullptr;
+  DevBuf<uint64_t> d_ip;
   // radix IP table (few /16 prefixes): prefix -> block, blocks of 64k u32 entries
-  uint16_t *d_rpre = nullptr;
-  uint32_t *d_rblk = nullptr;
-  size_t rblk_alloc = 0;
+  DevBuf<uint16_t> d_rpre;
+  DevBuf<uint32_t> d_rblk;
   bool radix = false;
   uint32_t radix_n = 0;                   // prefixes (blocks) of the radix table
   uint32_t radix_pfx[kRadixSmall / 2] = {};  // their values when radix_n <= kRadixSmall
   size_t ip_cap = 0;  // slots
   uint32_t ip_seed = 0;
-  // LDS image of the IP table for the tier-1 dense kernel (empty: not available)
-  uint8_t *d_ipl = nullptr;
-  size_t ipl_alloc = 0;
+  // LDS images of the IP table (build_lds_image; bytes 0: not available): the local pods for
+  // the tier-1 dense kernel, and every pod IP incl. the apiserver (sketch pass, wide_kernel)
+  DevBuf<uint8_t> d_ipl, d_ipl_all;
+  IpImage ipl{}, ipl_all{};
   // Hubble ipcache image (gpuagg_hubble.hip)
-  uint4 *d_ipc = nullptr;
+  DevBuf<uint4> d_ipc;
   size_t ipc_cap = 0;
   uint32_t ipc_seed = 0, ipc_max_probe = 0;
   // node-apiserver latency join (gpuagg_latency.hip)
   uint32_t lat_enabled = 0;  // bit 0 latency, 1 handshake, 2 no_response
   std::vector<uint32_t> api_ips;
-  uint32_t *d_api = nullptr;
-  unsigned long long *d_lat = nullptr;  // kLatStateWords
-  uint32_t *d_lat_blk_cnt = nullptr;
-  unsigned long long *d_lat_blk_max = nullptr, *d_lat_blk_clk = nullptr;
-  uint64_t *d_lat_blk_base = nullptr;
-  size_t lat_blk_alloc = 0;
-  LatEvent *d_lat_ev = nullptr;
-  size_t lat_ev_alloc = 0;
-  unsigned long long *d_lat_hash = nullptr;  // [2][lat_ev_alloc]: sort in, sort out
-  uint32_t *d_lat_idx = nullptr;
-  LatEvent *d_lat_carry[2] = {nullptr, nullptr};
-  size_t lat_carry_alloc = 0;
+  DevBuf<uint32_t> d_api;
+  DevBuf<unsigned long long> d_lat;  // kLatStateWords
+  DevBuf<uint32_t> d_lat_blk_cnt;    // the per-unit arrays: kLatMaxUnits each
+  DevBuf<unsigned long long> d_lat_blk_max, d_lat_blk_clk;
+  DevBuf<uint64_t> d_lat_blk_base;
+  DevBuf<LatEvent> d_lat_ev;
+  DevBuf<unsigned long long> d_lat_hash;  // [2][d_lat_ev.cap]: sort in, sort out
+  DevBuf<uint32_t> d_lat_idx;
+  DevBuf<LatEvent> d_lat_carry[2];
   int lat_carry_cur = 0;
   uint64_t lat_carry_bound = 0;  // >= entries currently carried
-  void *d_lat_tmp = nullptr;
-  size_t lat_tmp_alloc = 0;
+  DevBuf<uint8_t> d_lat_tmp;     // the sorts' scratch, bytes
   // capacity (ttlcache LIMIT): live-count check buffers and the sequential pass's ttlcache
-  int32_t *d_lat_delta = nullptr;   // [2][lat_ev_alloc + 1]: entry lives, live counts
-  int32_t *d_lat_max_live = nullptr;
-  unsigned long long *d_lat_okeys = nullptr;  // carried entries' LRU sort: [2][lat_carry_alloc]
-  uint32_t *d_lat_ovals = nullptr;
-  size_t lat_order_alloc = 0;
-  uint64_t *h_lat_n = nullptr;   // pinned: state words [kLatPending, kLatEvents] of the batch
-                                 // and, at [kLatReadWords], the batch's live-count maximum
+  DevBuf<int32_t> d_lat_delta;   // [2][d_lat_ev.cap + 1]: entry lives, live counts
+  DevBuf<int32_t> d_lat_max_live;
+  DevBuf<unsigned long long> d_lat_okeys;  // carried entries' LRU sort: [2][pending]
+  DevBuf<uint32_t> d_lat_ovals;
+  HostBuf<uint64_t> h_lat_n;  // pinned: state words [kLatPending, kLatEvents] of the batch
+                              // and, at [kLatReadWords], the batch's live-count maximum
   // the last batch's capacity decision, read at the next synchronisation (lat_resolve)
   struct LatPend {
     bool active = false;
@@ -366,40 +435,31 @@ struct gpuagg_ctx {
   } lat_pend;
   uint64_t lat_peak_pending = 0; // most requests carried into a batch since the reconcile
   int64_t time_offset = 0;       // ktime.MonotonicOffset added to decoded record times
-  uint8_t *d_ipl_all = nullptr;  // every pod IP incl. the apiserver (sketch pass)
-  size_t ipl_all_alloc = 0;
-  uint32_t ipl_all_nb = 0, ipl_all_seed = 0, ipl_all_bytes = 0;
-  bool ipl_all_radix = false, ipl_all_dense = false;  // image form (build_lds_image)
-  uint32_t ipl_all_npfx = 0, ipl_all_pfx[kIprMaxPfx] = {}, ipl_all_dr[kIprMaxPfx] = {};
-  uint32_t ipl_nb = 0, ipl_seed = 0, ipl_bytes = 0;
-  // the tier-1 image: dense radix, radix or cuckoo form (build_lds_image)
-  bool ipl_radix = false, ipl_dense = false;
-  uint32_t ipl_npfx = 0, ipl_pfx[kIprMaxPfx] = {}, ipl_dr[kIprMaxPfx] = {};
   uint64_t ip_version = 0;
 
   // dense counters
-  uint64_t *d_dense_cnt = nullptr, *d_dense_byt = nullptr;
+  DevBuf<uint64_t> d_dense_cnt, d_dense_byt;
   size_t dense_len = 0;
 
-  // sparse table
+  // sparse table: sv views d_table (k1, k2, cnt, byt point into the same array) and d_dropped
   SparseView sv{};
+  DevBuf<uint64_t> d_table, d_dropped;
   size_t sparse_slots = 0;
-  uint64_t *d_counter = nullptr;  // export counter
-  uint64_t *d_export = nullptr;
-  size_t export_cap = 0;
+  DevBuf<uint64_t> d_counter;  // export counter
+  DevBuf<uint64_t> d_export;   // kSparseEntryWords per slot of the table it was sized for
   // growth mode (gpuagg_set_sparse_growth): the table doubles up to 2^grow_max_log2 slots;
   // d_overflow is the list full segments append to (sv.overflow points at it while the
   // table can still grow, else it is null and a full segment loses the update as without
   // growth)
   uint32_t grow_max_log2 = 0;  // 0: off
   uint64_t grow_entries = 0;   // overflow list capacity, entries
-  uint64_t *d_overflow = nullptr;
+  DevBuf<uint64_t> d_overflow;
   uint64_t sparse_grows = 0, overflow_replayed = 0;
   const char *regrow_kernel = "";  // what rebuilt the table at the last grow (gpuagg_regrow_kernel_name)
   // pinned: settle_sparse's readback [kSparseWords], then the overflow fill copied back
   // behind every launch (ovf_event recorded after it; ovf_armed: a copy is in flight or done)
-  uint64_t *h_grow_words = nullptr;
-  hipEvent_t ovf_event = nullptr;
+  HostBuf<uint64_t> h_grow_words;
+  Event ovf_event;
   bool ovf_armed = false;
 
   // delta snapshots (gpuagg_snapshot_delta): the "published" shadow of the state -- what
@@ -409,13 +469,12 @@ struct gpuagg_ctx {
   // delta code, so a ctx that never asks for a delta pays nothing.
   struct Delta {
     bool active = false;
-    uint64_t *d_sparse = nullptr;  // per table slot: (count, bytes) wide, count compact
+    DevBuf<uint64_t> d_sparse;  // per table slot: (count, bytes) wide, count compact
     size_t slots = 0;
-    uint64_t *d_cnt = nullptr, *d_byt = nullptr;  // per dense bin
+    DevBuf<uint64_t> d_cnt, d_byt;  // per dense bin
     size_t bins = 0;
-    uint64_t *d_bins_out = nullptr;  // dense_delta's output, kDenseDeltaWords per bin
-    size_t bins_out_cap = 0;
-    uint64_t *d_ctr = nullptr;  // the scans' append counter (device mode)
+    DevBuf<uint64_t> d_bins_out;  // dense_delta's output, kDenseDeltaWords per bin
+    DevBuf<uint64_t> d_ctr;       // the scans' append counter (device mode)
     // changed entries scanned off a table about to be rebuilt (growth, retire): the shadow is
     // positional, so they wait here for the next delta and the new table's shadow is rebased
     std::vector<uint64_t> carry;
@@ -423,38 +482,34 @@ struct gpuagg_ctx {
   } delta;
 
   // sketches
-  uint32_t *d_cms = nullptr;
+  DevBuf<uint32_t> d_cms;
   size_t cms_len = 0;
-  uint8_t *d_hll = nullptr;
+  DevBuf<uint8_t> d_hll;
   size_t hll_len = 0;
   std::vector<uint32_t> h_cms;
   std::vector<uint8_t> h_hll;
   // heavy hitters (gpuagg_set_heavy_hitters; off while hh_min == 0): the candidate table of
   // gpuagg_hh.hip -- 2^hh_log2 slots of a 16-byte key and a tag word -- or, CPU backend, a set
   uint32_t hh_min = 0, hh_log2 = 0;
-  uint4 *d_hh_keys = nullptr;
-  uint32_t *d_hh_tags = nullptr;
-  uint64_t *d_hh_words = nullptr;  // kHhWords
+  DevBuf<uint4> d_hh_keys;
+  DevBuf<uint32_t> d_hh_tags;
+  DevBuf<uint64_t> d_hh_words;  // kHhWords
   gpuagg::cpu::HhSet hh_cpu;
 
   // Device staging for host-fed batches, double-buffered: batch k+1's H2D copy (on
   // copy_stream) overlaps batch k's aggregation (on stream).  `copied` is recorded on
   // copy_stream after the copy, `released` on stream after the last kernel reading it.
   struct Staging {
-    uint32_t *cols[6] = {};
-    uint32_t *tcp_id = nullptr;  // latency columns
-    uint64_t *time_ns = nullptr;
-    uint8_t *raw = nullptr;
-    size_t raw_alloc = 0;
-    hipEvent_t copied = nullptr, released = nullptr;
+    DevBuf<uint32_t> cols[6];
+    DevBuf<uint32_t> tcp_id;  // latency columns
+    DevBuf<uint64_t> time_ns;
+    DevBuf<uint8_t> raw;
+    Event copied, released;
     bool in_use = false;
   } stg[2];
   size_t staging_cap = 0;
   int next_stg = 0;
-  hipStream_t copy_stream = nullptr;
-  // deferred folds: the spill-window fold beside the segment fold (launch_folds' ForkJoin)
-  hipStream_t fold_stream = nullptr;
-  hipEvent_t fold_fork = nullptr, fold_join = nullptr;
+  Event fold_fork, fold_join;  // fold_stream's
   std::vector<gpuagg_batch *> batches;
   std::string kernel_name;  // aggregation kernel of the last launch (rocprofv3 spelling)
   std::string sketch_kernel_name;  // kernels of the last sketch pass, joined by "+"
@@ -470,14 +525,10 @@ struct gpuagg_ctx {
   bool tm_chain = false;
   uint32_t n_cu = 256;
   // dense spill lists (per workgroup) for bins beyond the LDS window
-  uint32_t *d_spill = nullptr;
-  size_t spill_alloc = 0;
-  uint32_t *d_spill_count = nullptr;
-  size_t spill_count_alloc = 0;
+  DevBuf<uint32_t> d_spill, d_spill_count;
   // staged flushes: per-workgroup LDS bins (tier-1) and per-partition fold windows
-  uint32_t *d_stage_a = nullptr;
-  size_t stage_a_alloc = 0;
-  uint32_t *d_fold_flag = nullptr;  // device-conditional wide-list folds: [2] fullest list
+  DevBuf<uint32_t> d_stage_a;
+  DevBuf<uint32_t> d_fold_flag;  // device-conditional wide-list folds: [2] fullest list
   uint32_t fold_parity = 0;
   // Deferred list folds: the spill / segment lists of consecutive launches with one
   // geometry accumulate and are folded once (fold_pending) -- per scrape epoch rather
@@ -498,38 +549,25 @@ struct gpuagg_ctx {
   } sk_pend;
   bool defer_folds = true;
   uint64_t wide_list_bytes = 0;  // wide-key list budget (gpuagg_create)
-  std::vector<std::array<hipEvent_t, 2>> pending_fold;  // deferred fold start, end
-  int32_t *d_enrich = nullptr;  // gpuagg_submit_enrich: [2][cap] endpoint slots
-  size_t enrich_alloc = 0;
-  hipEvent_t enrich_done = nullptr;
-  uint64_t *d_stage_b = nullptr;
-  size_t stage_b_alloc = 0;
+  SpanList pending_fold;  // deferred fold start, end
+  DevBuf<int32_t> d_enrich;  // gpuagg_submit_enrich: [2][cap] endpoint slots
+  Event enrich_done;
+  DevBuf<uint64_t> d_stage_b;
   // raw perf-record decode (gpuagg_decode.hip)
-  uint64_t *d_decode_oor = nullptr;  // out-of-range field counter
-  std::vector<std::array<hipEvent_t, 2>> pending_decode;  // decode start, end
+  DevBuf<uint64_t> d_decode_oor;  // out-of-range field counter
+  SpanList pending_decode;        // decode start, end
   // sketch pass (count-min window lists)
-  uint16_t *d_sk_lists = nullptr;
-  size_t sk_lists_alloc = 0;
-  uint32_t *d_sk_counts = nullptr;
-  size_t sk_counts_alloc = 0;
-  uint64_t *d_sp_lists = nullptr;
-  size_t sp_lists_alloc = 0;
-  uint32_t *d_sp_counts = nullptr;
-  size_t sp_counts_alloc = 0;
-  uint32_t *d_hll_lists = nullptr;
-  size_t hll_lists_alloc = 0;
-  uint32_t *d_hll_counts = nullptr;
-  size_t hll_counts_alloc = 0;
-  uint32_t *d_hll_lists2 = nullptr;
-  size_t hll_lists2_alloc = 0;
-  uint32_t *d_hll_counts2 = nullptr;
-  size_t hll_counts2_alloc = 0;
-  std::vector<std::array<hipEvent_t, 2>> pending_sketch;  // sketch scatter launch start, end
+  DevBuf<uint16_t> d_sk_lists;
+  DevBuf<uint32_t> d_sk_counts;
+  DevBuf<uint64_t> d_sp_lists;
+  DevBuf<uint32_t> d_sp_counts;
+  DevBuf<uint32_t> d_hll_lists, d_hll_counts, d_hll_lists2, d_hll_counts2;
+  SpanList pending_sketch;  // sketch scatter launch start, end
   uint64_t pending_sketch_submits = 0;  // submits those launches belong to (sketch_launches)
   // node-wide feeds over this context (gpuagg_feed.cpp): detached by gpuagg_destroy
   std::vector<gpuagg_raw_feed *> feeds;
   uint64_t host_decode_oor = 0;  // out-of-range rows the feeds decoded on the host
-  uint64_t *h_sync_words = nullptr;  // pinned: gpuagg_sync's counter readback [decode oor, sparse dropped]
+  HostBuf<uint64_t> h_sync_words;  // pinned: gpuagg_sync's counter readback [decode oor, sparse dropped]
 };
 
 // ------------------------------------------------------------------------------------
@@ -593,41 +631,42 @@ void x_host_free(gpuagg_ctx *c, void *p) {
 }
 
 template <class T>
-int dev_alloc(gpuagg_ctx *c, T **p, size_t count) {
-  *p = nullptr;
+int DevBuf<T>::alloc(gpuagg_ctx *c, size_t count) {
+  reset();
   if (!count) return GPUAGG_OK;
-  if (c->cpu) {  // 64-byte aligned like device allocations (vector loads, 16-byte slots)
+  host = c->cpu != nullptr;
+  if (host) {  // 64-byte aligned like device allocations (vector loads, 16-byte slots)
     const size_t bytes = (count * sizeof(T) + 63) & ~(size_t)63;
     void *q = aligned_alloc(64, bytes);
     if (!q) return fail(c, GPUAGG_ENOMEM, "aligned_alloc(%zu bytes)", bytes);
     memset(q, 0, bytes);
-    *p = (T *)q;
-    return GPUAGG_OK;
+    p = (T *)q;
+  } else {
+    hipError_t e = hipMalloc((void **)&p, count * sizeof(T));
+    if (e != hipSuccess) {
+      p = nullptr;
+      return fail(c, GPUAGG_ENOMEM, "hipMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e));
+    }
   }
-  hipError_t e = hipMalloc((void **)p, count * sizeof(T));
-  if (e != hipSuccess)
-    return fail(c, GPUAGG_ENOMEM, "hipMalloc(%zu bytes): %s", count * sizeof(T), hipGetErrorString(e));
+  cap = count;
   return GPUAGG_OK;
 }
 
 template <class T>
-void dev_free(gpuagg_ctx *c, T *&p) {
-  if (p) {
-    if (c->cpu) free((void *)p);
-    else hipFree((void *)p);
-  }
-  p = nullptr;
+int DevBuf<T>::ensure(gpuagg_ctx *c, size_t count) {
+  if (count <= cap) return GPUAGG_OK;
+  if (p) (void)x_sync(c, c->stream);  // in-flight launches may still use the old buffer
+  return alloc(c, count);
 }
 
-// Grows a lazily allocated device buffer to at least `count` elements.
 template <class T>
-int ensure_buf(gpuagg_ctx *c, T **p, size_t *alloc, size_t count) {
-  if (count <= *alloc) return GPUAGG_OK;
-  if (*p) x_sync(c, c->stream);  // in-flight launches may still use the old buffer
-  dev_free(c, *p);
-  *alloc = 0;
-  if (int rc = dev_alloc(c, p, count)) return rc;
-  *alloc = count;
+int HostBuf<T>::ensure(gpuagg_ctx *c, size_t count) {
+  if (p) return GPUAGG_OK;
+  if (x_host_alloc(c, (void **)&p, count * sizeof(T)) != hipSuccess) {
+    p = nullptr;
+    return fail(c, GPUAGG_ENOMEM, "pinned host allocation (%zu bytes)", count * sizeof(T));
+  }
+  pinned = !c->cpu;
   return GPUAGG_OK;
 }
 
@@ -696,13 +735,10 @@ int ensure_staging(gpuagg_ctx *c, size_t cap) {
   }
   c->staging_cap = 0;
   for (auto &s : c->stg) {
-    for (auto &p : s.cols) dev_free(c, p);
-    dev_free(c, s.tcp_id);
-    dev_free(c, s.time_ns);
     for (auto &p : s.cols)
-      if (int rc = dev_alloc(c, &p, cap)) return rc;
-    if (int rc = dev_alloc(c, &s.tcp_id, cap)) return rc;
-    if (int rc = dev_alloc(c, &s.time_ns, cap)) return rc;
+      if (int rc = p.alloc(c, cap)) return rc;
+    if (int rc = s.tcp_id.alloc(c, cap)) return rc;
+    if (int rc = s.time_ns.alloc(c, cap)) return rc;
   }
   c->staging_cap = cap;
   return GPUAGG_OK;
@@ -747,6 +783,22 @@ int run_staged(gpuagg_ctx *c, gpuagg_ctx::Staging &s, F &&launch_fn, hipEvent_t 
 // these events.
 constexpr unsigned kTimingEventFlags = hipEventDisableSystemFence;
 
+// A span is open only while timing is on (gpuagg_set_timing); an event created before a
+// later step fails goes with the Span.
+int span_open(gpuagg_ctx *c, Span &sp) {
+  if (!c->timing) return GPUAGG_OK;
+  for (auto &e : sp.ev) HIPCHK(c, hipEventCreateWithFlags(&e, kTimingEventFlags));
+  HIPCHK(c, hipEventRecord(sp.ev[0], c->stream));
+  return GPUAGG_OK;
+}
+int span_close(gpuagg_ctx *c, Span &sp, SpanList &to) {
+  if (!sp.ev[0]) return GPUAGG_OK;
+  HIPCHK(c, hipEventRecord(sp.ev[1], c->stream));
+  to.push_back(sp.ev);
+  sp.ev = {};
+  return GPUAGG_OK;
+}
+
 // Folds the lists of the deferred launches (no-op when none are waiting).  Every reader
 // of the counters or the group-by table calls it first: gpuagg_sync (and through it the
 // snapshot), state export, merge, slot retirement and dense re-layout.
@@ -756,9 +808,9 @@ int fold_pending_sketch(gpuagg_ctx *c);
 int fold_fork_join(gpuagg_ctx *c, ForkJoin *fj) {
   if (!c->fold_stream) {
     HIPCHK(c, hipStreamCreateWithFlags(&c->fold_stream, hipStreamNonBlocking));
-    HIPCHK(c, hipEventCreateWithFlags(&c->fold_fork, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&c->fold_join, hipEventDisableTiming));
   }
+  HIPCHK(c, c->fold_fork.create(hipEventDisableTiming));
+  HIPCHK(c, c->fold_join.create(hipEventDisableTiming));
   *fj = ForkJoin{c->fold_stream, c->fold_fork, c->fold_join};
   return GPUAGG_OK;
 }
@@ -773,22 +825,15 @@ int fold_pending_dense(gpuagg_ctx *c) {
   f.stage_accum = false;
   f.defer_folds = false;
   f.fold_cond = false;  // unconditional (the flags are left to the launches)
-  std::array<hipEvent_t, 2> ev{};
-  if (c->timing) {
-    for (auto &e : ev) HIPCHK(c, hipEventCreateWithFlags(&e, kTimingEventFlags));
-    HIPCHK(c, hipEventRecord(ev[0], c->stream));
-  }
+  Span sp;
+  if (int rc = span_open(c, sp)) return rc;
   ENQ(c);
   ForkJoin fj{};
   const bool fork = f.sp_lists && f.sparse.compact && f.spill;
   if (fork)
     if (int rc = fold_fork_join(c, &fj)) return rc;
   HIPCHK(c, launch_folds(f, c->stream, fork ? &fj : nullptr));
-  if (c->timing) {
-    HIPCHK(c, hipEventRecord(ev[1], c->stream));
-    c->pending_fold.push_back(ev);
-  }
-  return GPUAGG_OK;
+  return span_close(c, sp, c->pending_fold);
 }
 
 int lat_resolve(gpuagg_ctx *c);
@@ -812,6 +857,12 @@ void drop_pending(gpuagg_ctx *c) {
 
 void delta_drop(gpuagg_ctx *c);
 
+// The HBM IP table as the launches read it (the radix form while the IPs allow one).
+IpTableView ip_table(const gpuagg_ctx *c) {
+  return IpTableView{c->d_ip, (uint32_t)(c->ip_cap ? c->ip_cap / 2 - 1 : 0), c->ip_seed,
+                     c->radix ? c->d_rpre.p : nullptr, c->radix ? c->d_rblk.p : nullptr};
+}
+
 // ---- heavy-hitter candidates (gpuagg_hh.hip) -------------------------------------------------
 HhTable hh_table(const gpuagg_ctx *c) {
   return HhTable{c->d_hh_keys, c->d_hh_tags, (uint32_t)(((size_t)1 << c->hh_log2) - 1), c->d_hh_words,
@@ -830,9 +881,9 @@ int hh_clear(gpuagg_ctx *c) {
   return GPUAGG_OK;
 }
 void hh_free(gpuagg_ctx *c) {
-  dev_free(c, c->d_hh_keys);
-  dev_free(c, c->d_hh_tags);
-  dev_free(c, c->d_hh_words);
+  c->d_hh_keys.reset();
+  c->d_hh_tags.reset();
+  c->d_hh_words.reset();
   c->hh_cpu = gpuagg::cpu::HhSet{};
   c->hh_min = c->hh_log2 = 0;
 }
@@ -875,7 +926,7 @@ int ensure_overflow(gpuagg_ctx *c) {
   if (!c->sparse_slots) return GPUAGG_OK;
   c->sv.overflow = nullptr;
   if (c->grow_max_log2 && !c->d_overflow) {
-    if (int rc = dev_alloc(c, &c->d_overflow, kOverflowHeaderWords + c->grow_entries * kSparseEntryWords)) return rc;
+    if (int rc = c->d_overflow.alloc(c, kOverflowHeaderWords + c->grow_entries * kSparseEntryWords)) return rc;
     const uint64_t hdr[kOverflowHeaderWords] = {0, c->grow_entries};
     HIPCHK(c, x_copy(c, c->d_overflow, hdr, sizeof hdr, hipMemcpyHostToDevice));
   }
@@ -895,9 +946,11 @@ int ensure_sparse(gpuagg_ctx *c) {
   int rc;
   // one interleaved array: slot h = words [5h, 5h + 5) = k0 k1 k2 cnt byt (kSparseSlotWords)
   // (sv.dropped: the lost-update counter, then the words settle_sparse reads back with it)
-  if ((rc = dev_alloc(c, &c->sv.k0, n * kSparseSlotWords)) || (rc = dev_alloc(c, &c->sv.dropped, kSparseWords)) ||
-      (rc = dev_alloc(c, &c->d_counter, 1)))
+  if ((rc = c->d_table.alloc(c, n * kSparseSlotWords)) || (rc = c->d_dropped.alloc(c, kSparseWords)) ||
+      (rc = c->d_counter.alloc(c, 1)))
     return rc;
+  c->sv.k0 = c->d_table;
+  c->sv.dropped = c->d_dropped;
   // (device allocations are not zeroed: no list address before ensure_overflow writes one)
   const uint64_t zero[kSparseWords] = {};
   HIPCHK(c, x_copy(c, c->sv.dropped, zero, sizeof zero, hipMemcpyHostToDevice));
@@ -912,14 +965,8 @@ int ensure_sparse(gpuagg_ctx *c) {
 }
 
 // The ctx's own export buffer d_export, one entry per slot of the current table.
-int ensure_export(gpuagg_ctx *c) {
-  if (c->export_cap >= c->sparse_slots) return GPUAGG_OK;
-  dev_free(c, c->d_export);
-  c->export_cap = 0;
-  if (int rc = dev_alloc(c, &c->d_export, c->sparse_slots * kSparseEntryWords)) return rc;
-  c->export_cap = c->sparse_slots;
-  return GPUAGG_OK;
-}
+int ensure_export(gpuagg_ctx *c) { return c->d_export.ensure(c, c->sparse_slots * kSparseEntryWords); }
+size_t export_cap(const gpuagg_ctx *c) { return c->d_export.cap / kSparseEntryWords; }  // entries
 
 // ---- delta snapshots: the shadow and what keeps it true -----------------------------------
 // Frees the baseline: the next gpuagg_snapshot_delta starts from zero and says "rebased".
@@ -927,12 +974,8 @@ void delta_drop(gpuagg_ctx *c) {
   gpuagg_ctx::Delta &d = c->delta;
   if (!d.active) return;
   (void)x_sync(c, c->stream);
-  dev_free(c, d.d_sparse);
-  dev_free(c, d.d_cnt);
-  dev_free(c, d.d_byt);
-  dev_free(c, d.d_bins_out);
-  dev_free(c, d.d_ctr);
-  d.slots = d.bins = d.bins_out_cap = 0;
+  for (DevBuf<uint64_t> *b : {&d.d_sparse, &d.d_cnt, &d.d_byt, &d.d_bins_out, &d.d_ctr}) b->reset();
+  d.slots = d.bins = 0;
   std::vector<uint64_t>().swap(d.carry);
   d.active = false;
 }
@@ -946,15 +989,15 @@ int delta_scan_sparse(gpuagg_ctx *c, std::vector<uint64_t> &dst, uint64_t *n_out
   if (int rc = ensure_export(c)) return rc;
   uint64_t n = 0;
   if (c->cpu) {
-    n = cpu::sparse_delta(c->sv, c->sparse_slots, d.d_sparse, c->d_export, c->export_cap);
+    n = cpu::sparse_delta(c->sv, c->sparse_slots, d.d_sparse, c->d_export, export_cap(c));
   } else {
     HIPCHK(c, x_set_async(c, d.d_ctr, 0, 8, c->stream));
     ENQ(c);
-    HIPCHK(c, launch_sparse_delta(c->sv, c->sparse_slots, d.d_sparse, c->d_export, c->export_cap, d.d_ctr, c->stream));
+    HIPCHK(c, launch_sparse_delta(c->sv, c->sparse_slots, d.d_sparse, c->d_export, export_cap(c), d.d_ctr, c->stream));
     HIPCHK(c, x_copy_async(c, &n, d.d_ctr, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, x_sync(c, c->stream));
   }
-  if (n > c->export_cap) return fail(c, GPUAGG_ESTATE, "delta scan emitted %llu entries from %zu slots",
+  if (n > export_cap(c)) return fail(c, GPUAGG_ESTATE, "delta scan emitted %llu entries from %zu slots",
                                      (unsigned long long)n, c->sparse_slots);
   if (n) {
     const size_t o = dst.size();
@@ -983,9 +1026,8 @@ int delta_rebase(gpuagg_ctx *c) {
   if (!d.active || !d.d_sparse) return GPUAGG_OK;
   int rc = GPUAGG_OK;
   if (d.slots != c->sparse_slots) {
-    dev_free(c, d.d_sparse);
     d.slots = 0;
-    if ((rc = dev_alloc(c, &d.d_sparse, c->sparse_slots * (c->sv.compact ? 1 : 2))) == GPUAGG_OK)
+    if ((rc = d.d_sparse.alloc(c, c->sparse_slots * (c->sv.compact ? 1 : 2))) == GPUAGG_OK)
       d.slots = c->sparse_slots;
   }
   if (rc == GPUAGG_OK) {
@@ -1007,8 +1049,8 @@ int delta_rebase(gpuagg_ctx *c) {
 // allocated the old one stays as it is.
 int grow_sparse(gpuagg_ctx *c, uint32_t new_lg) {
   const size_t n = (size_t)1 << new_lg;
-  uint64_t *k0 = nullptr;
-  if (int rc = dev_alloc(c, &k0, n * kSparseSlotWords)) return rc;
+  DevBuf<uint64_t> k0;
+  if (int rc = k0.alloc(c, n * kSparseSlotWords)) return rc;
   SparseView nv = c->sv;
   nv.k0 = k0;
   nv.k1 = k0 + 1;
@@ -1032,12 +1074,10 @@ int grow_sparse(gpuagg_ctx *c, uint32_t new_lg) {
     hipError_t e = launch_sparse_init(nv, n, c->stream);
     if (e == hipSuccess) e = launch_sparse_regrow(c->sv, c->sparse_slots, nv, n, direct, c->stream);
     if (e == hipSuccess) e = x_sync(c, c->stream);
-    if (e != hipSuccess) {
-      dev_free(c, k0);
+    if (e != hipSuccess)
       return fail(c, GPUAGG_EDEVICE, "group-by table regrow to 2^%u: %s", new_lg, hipGetErrorString(e));
-    }
   }
-  dev_free(c, c->sv.k0);
+  c->d_table = std::move(k0);
   c->sv = nv;
   c->sparse_slots = n;
   c->sparse_grows += 1;
@@ -1057,7 +1097,7 @@ int settle_sparse(gpuagg_ctx *c) {
   if (int rc = fold_pending(c)) return rc;
   if (!c->grow_max_log2 || !c->sparse_slots) return GPUAGG_OK;
   c->ovf_armed = false;
-  if (!c->h_grow_words) HIPCHK(c, x_host_alloc(c, (void **)&c->h_grow_words, (kSparseWords + 1) * 8));
+  if (int rc = c->h_grow_words.ensure(c, kSparseWords + 1)) return rc;
   uint64_t *w = c->h_grow_words;
   for (;;) {  // at most grow_max_log2 - lg rounds
     const uint32_t lg = (uint32_t)__builtin_ctzll(c->sparse_slots);
@@ -1079,15 +1119,14 @@ int settle_sparse(gpuagg_ctx *c) {
     if (int rc = grow_sparse(c, new_lg)) return rc;
     if (!fill) continue;
     // the list is read from a copy: an entry that overflows again is appended to it
-    uint64_t *tmp = nullptr;
-    if (int rc = dev_alloc(c, &tmp, fill * kSparseEntryWords)) return rc;  // (the list keeps its entries)
+    DevBuf<uint64_t> tmp;
+    if (int rc = tmp.alloc(c, fill * kSparseEntryWords)) return rc;  // (the list keeps its entries)
     hipError_t e = x_copy_async(c, tmp, c->d_overflow + kOverflowHeaderWords, fill * kSparseEntryWords * 8,
                                 hipMemcpyDeviceToDevice, c->stream);
     if (e == hipSuccess) e = x_set_async(c, c->d_overflow, 0, 8, c->stream);
     if (c->cpu) cpu::sparse_import(c->sv, tmp, fill);
     else if (e == hipSuccess) e = launch_sparse_import(c->sv, tmp, fill, c->stream, true);
     if (e == hipSuccess) e = x_sync(c, c->stream);
-    dev_free(c, tmp);
     if (e != hipSuccess) return fail(c, GPUAGG_EDEVICE, "overflow list replay: %s", hipGetErrorString(e));
     c->overflow_replayed += fill;
   }
@@ -1100,7 +1139,7 @@ int export_table(gpuagg_ctx *c, size_t *n_out) {
   *n_out = 0;
   if (int rc = settle_sparse(c)) return rc;
   if (int rc = ensure_export(c)) return rc;
-  return gpuagg_sparse_export(c, c->d_export, c->export_cap, n_out);
+  return gpuagg_sparse_export(c, c->d_export, export_cap(c), n_out);
 }
 
 // Slots covered by the dense counters / HLL rows for n interned slots: whole 64-slot
@@ -1136,11 +1175,8 @@ int layout_dense(gpuagg_ctx *c, uint32_t key_cap, bool keep) {
   if (total >= (1ull << 32)) return fail(c, GPUAGG_ECAPACITY, "dense counter space >= 2^32 bins");
   HIPCHK(c, x_sync(c, c->stream));
   int rc;
-  uint64_t *cnt = nullptr, *byt = nullptr;
-  if ((rc = dev_alloc(c, &cnt, total)) || (rc = dev_alloc(c, &byt, total))) {
-    dev_free(c, cnt);
-    return rc;
-  }
+  DevBuf<uint64_t> cnt, byt;
+  if ((rc = cnt.alloc(c, total)) || (rc = byt.alloc(c, total))) return rc;
   if (total) {
     HIPCHK(c, x_set_async(c, cnt, 0, total * 8, c->stream));
     HIPCHK(c, x_set_async(c, byt, 0, total * 8, c->stream));
@@ -1153,18 +1189,13 @@ int layout_dense(gpuagg_ctx *c, uint32_t key_cap, bool keep) {
   }
   if (c->cfg.hll_precision) {
     const size_t len = (size_t)key_cap << c->cfg.hll_precision;
-    uint8_t *hll = nullptr;
-    if ((rc = dev_alloc(c, &hll, len))) {
-      dev_free(c, cnt);
-      dev_free(c, byt);
-      return rc;
-    }
+    DevBuf<uint8_t> hll;
+    if ((rc = hll.alloc(c, len))) return rc;
     HIPCHK(c, x_set_async(c, hll, 0, len, c->stream));
     if (keep && c->hll_len)
       HIPCHK(c, x_copy_async(c, hll, c->d_hll, std::min(len, c->hll_len), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, x_sync(c, c->stream));
-    dev_free(c, c->d_hll);
-    c->d_hll = hll;
+    c->d_hll = std::move(hll);
     c->hll_len = len;
   }
   // a delta baseline's shadow arrays move exactly as the counters do; if the larger ones
@@ -1172,9 +1203,8 @@ int layout_dense(gpuagg_ctx *c, uint32_t key_cap, bool keep) {
   int drc = GPUAGG_OK;
   gpuagg_ctx::Delta &dl = c->delta;
   if (dl.active && dl.d_cnt) {
-    uint64_t *scnt = nullptr, *sbyt = nullptr;
-    if ((drc = dev_alloc(c, &scnt, total)) || (drc = dev_alloc(c, &sbyt, total))) {
-      dev_free(c, scnt);
+    DevBuf<uint64_t> scnt, sbyt;
+    if ((drc = scnt.alloc(c, total)) || (drc = sbyt.alloc(c, total))) {
       delta_drop(c);
     } else {
       hipError_t e = hipSuccess;
@@ -1189,24 +1219,18 @@ int layout_dense(gpuagg_ctx *c, uint32_t key_cap, bool keep) {
       }
       if (e == hipSuccess) e = x_sync(c, c->stream);
       if (e != hipSuccess) {
-        dev_free(c, scnt);
-        dev_free(c, sbyt);
         delta_drop(c);
         drc = fail(c, GPUAGG_EDEVICE, "delta shadow re-layout: %s", hipGetErrorString(e));
       } else {
-        dev_free(c, dl.d_cnt);
-        dev_free(c, dl.d_byt);
-        dl.d_cnt = scnt;
-        dl.d_byt = sbyt;
+        dl.d_cnt = std::move(scnt);
+        dl.d_byt = std::move(sbyt);
         dl.bins = total;
       }
     }
   }
   HIPCHK(c, x_sync(c, c->stream));
-  dev_free(c, c->d_dense_cnt);
-  dev_free(c, c->d_dense_byt);
-  c->d_dense_cnt = cnt;
-  c->d_dense_byt = byt;
+  c->d_dense_cnt = std::move(cnt);
+  c->d_dense_byt = std::move(byt);
   c->dense_len = total;
   for (size_t g = 0; g < c->groups.size(); ++g) {
     Group &gr = c->groups[g];
@@ -1218,6 +1242,22 @@ int layout_dense(gpuagg_ctx *c, uint32_t key_cap, bool keep) {
   }
   c->key_cap = key_cap;
   return drc;
+}
+
+// Waits for each span of the list, adds its time to *ms and destroys its events; returns
+// the spans that were read.
+uint64_t drain_spans(SpanList &list, double *ms) {
+  uint64_t n = 0;
+  for (auto &ev : list) {
+    float t = 0.f;
+    if (hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) {
+      *ms += t;
+      ++n;
+    }
+    for (hipEvent_t e : ev) hipEventDestroy(e);
+  }
+  list.clear();
+  return n;
 }
 
 void drain_timing(gpuagg_ctx *c) {
@@ -1240,31 +1280,11 @@ void drain_timing(gpuagg_ctx *c) {
   c->pending_events.clear();
   c->tm_end = nullptr;
   c->tm_chain = false;
-  for (auto &ev : c->pending_decode) {
-    float ms = 0.f;
-    if (hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) {
-      c->stats.decode_ms += ms;
-      c->stats.decode_launches += 1;
-    }
-    for (hipEvent_t e : ev) hipEventDestroy(e);
-  }
-  c->pending_decode.clear();
-  for (auto &ev : c->pending_sketch) {
-    float ms = 0.f;
-    if (hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-      c->stats.sketch_ms += ms;
-    for (hipEvent_t e : ev) hipEventDestroy(e);
-  }
+  c->stats.decode_launches += drain_spans(c->pending_decode, &c->stats.decode_ms);
+  drain_spans(c->pending_sketch, &c->stats.sketch_ms);
   c->stats.sketch_launches += c->pending_sketch_submits;
   c->pending_sketch_submits = 0;
-  c->pending_sketch.clear();
-  for (auto &ev : c->pending_fold) {
-    float ms = 0.f;
-    if (hipEventSynchronize(ev[1]) == hipSuccess && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess)
-      c->stats.fold_ms += ms;
-    for (hipEvent_t e : ev) hipEventDestroy(e);
-  }
-  c->pending_fold.clear();
+  drain_spans(c->pending_fold, &c->stats.fold_ms);
 }
 
 // Count-min windows: 2^15 columns (128 KiB of LDS in the fold); at most 4096 windows
@@ -1290,8 +1310,8 @@ int size_hll_level2(gpuagg_ctx *c, SketchArgs &s, uint64_t records) {
   const uint64_t cap2 = (mean2 + mean2 / 4 + 64 + 15) & ~15ULL;
   const size_t n2 = (size_t)s.hll_nsup * s.hll_b2 * nfine;
   int rc;
-  if ((rc = ensure_buf(c, &c->d_hll_lists2, &c->hll_lists2_alloc, n2 * cap2))) return rc;
-  if ((rc = ensure_buf(c, &c->d_hll_counts2, &c->hll_counts2_alloc, n2))) return rc;
+  if ((rc = c->d_hll_lists2.ensure(c, n2 * cap2))) return rc;
+  if ((rc = c->d_hll_counts2.ensure(c, n2))) return rc;
   s.hll_cap2 = (uint32_t)cap2;
   s.hll_lists2 = c->d_hll_lists2;
   s.hll_counts2 = c->d_hll_counts2;
@@ -1307,20 +1327,13 @@ int fold_pending_sketch(gpuagg_ctx *c) {
   s.accum = false;
   int rc;
   if (s.hll_nsup && (rc = size_hll_level2(c, s, c->sk_pend.rpb * s.blocks))) return rc;
-  std::array<hipEvent_t, 2> ev{};
-  if (c->timing) {
-    for (auto &e : ev) HIPCHK(c, hipEventCreateWithFlags(&e, kTimingEventFlags));
-    HIPCHK(c, hipEventRecord(ev[0], c->stream));
-  }
+  Span sp;
+  if ((rc = span_open(c, sp))) return rc;
   ENQ(c);
   ForkJoin fj{};
   if (!c->cpu && (rc = fold_fork_join(c, &fj))) return rc;
   HIPCHK(c, launch_sketch(s, c->stream, nullptr, c->cpu ? nullptr : &fj));
-  if (c->timing) {
-    HIPCHK(c, hipEventRecord(ev[1], c->stream));
-    c->pending_fold.push_back(ev);
-  }
-  return GPUAGG_OK;
+  return span_close(c, sp, c->pending_fold);
 }
 
 // The waiting count-min lists alone folded into the rows (the heavy-hitter test of a submit
@@ -1344,11 +1357,7 @@ int hh_fold_cms(gpuagg_ctx *c) {
 int launch_sketches(gpuagg_ctx *c, const ColsView &cv, size_t n) {
   int rc;
   SketchArgs s{};
-  s.ip_slots = c->d_ip;
-  s.ip_mask = (uint32_t)(c->ip_cap ? c->ip_cap / 2 - 1 : 0);  // bucket mask
-  s.ip_pre = c->radix ? c->d_rpre : nullptr;
-  s.ip_blk = c->radix ? c->d_rblk : nullptr;
-  s.ip_seed = c->ip_seed;
+  s.ip = ip_table(c);
   s.cms = c->d_cms;
   s.cms_depth = c->cms_len ? c->cfg.cms_depth : 0;
   s.cms_wlog2 = c->cfg.cms_width_log2;
@@ -1364,19 +1373,7 @@ int launch_sketches(gpuagg_ctx *c, const ColsView &cv, size_t n) {
     if (c->hh_min) c->hh_cpu.pass(cv, n, c->d_cms, c->cfg.cms_depth, c->cfg.cms_width_log2, c->hh_min);
     return GPUAGG_OK;
   }
-  if (s.hll_p && c->ipl_all_bytes) {
-    s.ipl = c->d_ipl_all;
-    s.ipl_nb = c->ipl_all_nb;
-    s.ipl_seed = c->ipl_all_seed;
-    s.ipl_bytes = c->ipl_all_bytes;
-    s.ipl_radix = c->ipl_all_radix;
-    s.ipl_dense = c->ipl_all_dense;
-    s.ipl_npfx = c->ipl_all_npfx;
-    for (uint32_t j = 0; j < kIprMaxPfx; ++j) {
-      s.ipl_pfx[j] = c->ipl_all_pfx[j];
-      s.ipl_dr[j] = c->ipl_all_dr[j];
-    }
-  }
+  if (s.hll_p && c->ipl_all.bytes) s.ipl = c->ipl_all;
   // HLL bucketing: fine windows of 2^hll_shift pods (128 KiB of registers, the fold's
   // LDS), super-windows of 2^hll_sshift pods (~16 of them, the scatter's lists); pod bits
   // of an entry: 26 - p
@@ -1404,8 +1401,8 @@ int launch_sketches(gpuagg_ctx *c, const ColsView &cv, size_t n) {
     if (!direct && nwin && nwin <= kCmsMaxWindows) {
       const uint64_t mean = rpb * x.cms_depth / nwin;
       const uint64_t cap = (mean + mean / 8 + 2048 + 7) & ~7ULL;
-      if ((r = ensure_buf(c, &c->d_sk_lists, &c->sk_lists_alloc, (size_t)x.blocks * nwin * cap))) return r;
-      if ((r = ensure_buf(c, &c->d_sk_counts, &c->sk_counts_alloc, (size_t)x.blocks * nwin))) return r;
+      if ((r = c->d_sk_lists.ensure(c, (size_t)x.blocks * nwin * cap))) return r;
+      if ((r = c->d_sk_counts.ensure(c, (size_t)x.blocks * nwin))) return r;
       x.nwin = (uint32_t)nwin;
       x.cap = (uint32_t)cap;
       x.lists = c->d_sk_lists;
@@ -1416,8 +1413,8 @@ int launch_sketches(gpuagg_ctx *c, const ColsView &cv, size_t n) {
     if (hnsup) {
       const uint64_t mean = rpb / hnsup;
       const uint64_t cap = (mean + mean / 4 + 64 + 15) & ~15ULL;
-      if ((r = ensure_buf(c, &c->d_hll_lists, &c->hll_lists_alloc, (size_t)x.blocks * hnsup * cap))) return r;
-      if ((r = ensure_buf(c, &c->d_hll_counts, &c->hll_counts_alloc, (size_t)x.blocks * hnsup))) return r;
+      if ((r = c->d_hll_lists.ensure(c, (size_t)x.blocks * hnsup * cap))) return r;
+      if ((r = c->d_hll_counts.ensure(c, (size_t)x.blocks * hnsup))) return r;
       x.hll_nsup = (uint32_t)hnsup;
       x.hll_nwin = (uint32_t)hnwin;
       x.hll_cap = (uint32_t)cap;
@@ -1429,16 +1426,6 @@ int launch_sketches(gpuagg_ctx *c, const ColsView &cv, size_t n) {
   // Timing (gpuagg_set_timing): sketch_ms spans the scatter launches only -- the kernel
   // bench.py names -- and the folds count in fold_ms (fold_pending_sketch, or the pair
   // around a full-size launch's folds below); sketch_launches counts submits.
-  auto t_open = [&](std::array<hipEvent_t, 2> &ev) -> int {
-    for (auto &e : ev) HIPCHK(c, hipEventCreateWithFlags(&e, kTimingEventFlags));
-    HIPCHK(c, hipEventRecord(ev[0], c->stream));
-    return GPUAGG_OK;
-  };
-  auto t_close = [&](std::array<hipEvent_t, 2> &ev, std::vector<std::array<hipEvent_t, 2>> &to) -> int {
-    HIPCHK(c, hipEventRecord(ev[1], c->stream));
-    to.push_back(ev);
-    return GPUAGG_OK;
-  };
   if (c->timing) ++c->pending_sketch_submits;
   // Deferred folds (small launches, e.g. the Go plugin's 2^20 records: chunk 4096): the
   // folds' fixed passes -- every count-min row and the whole HLL register array (164 MB at
@@ -1483,10 +1470,10 @@ int launch_sketches(gpuagg_ctx *c, const ColsView &cv, size_t n) {
       s.passes = kSketchScatter;
       s.accum = accum;
       ENQ(c);
-      std::array<hipEvent_t, 2> ev{};
-      if (c->timing && (rc = t_open(ev))) return rc;
+      Span ev;
+      if ((rc = span_open(c, ev))) return rc;
       HIPCHK(c, launch_sketch(s, c->stream, &c->sketch_kernel_name));
-      if (c->timing && (rc = t_close(ev, c->pending_sketch))) return rc;
+      if ((rc = span_close(c, ev, c->pending_sketch))) return rc;
       c->sk_pend.rpb = (accum ? c->sk_pend.rpb : 0) + s.chunk;
       c->sk_pend.budget = kSketchDeferRecords;
       c->sk_pend.s = s;
@@ -1498,15 +1485,15 @@ int launch_sketches(gpuagg_ctx *c, const ColsView &cv, size_t n) {
     // the scatter, then its folds (kSketchBoth as two calls, so each is timed on its own)
     s.accum = false;
     ENQ(c);
-    std::array<hipEvent_t, 2> ev{}, evf{};
+    Span ev, evf;
     s.passes = kSketchScatter;
-    if (c->timing && (rc = t_open(ev))) return rc;
+    if ((rc = span_open(c, ev))) return rc;
     HIPCHK(c, launch_sketch(s, c->stream, &c->sketch_kernel_name));
-    if (c->timing && (rc = t_close(ev, c->pending_sketch))) return rc;
+    if ((rc = span_close(c, ev, c->pending_sketch))) return rc;
     s.passes = kSketchFolds;
-    if (c->timing && (rc = t_open(evf))) return rc;
+    if ((rc = span_open(c, evf))) return rc;
     HIPCHK(c, launch_sketch(s, c->stream, nullptr));
-    if (c->timing && (rc = t_close(evf, c->pending_fold))) return rc;
+    if ((rc = span_close(c, evf, c->pending_fold))) return rc;
   }
   // heavy hitters: every record of this submit against the rows that now hold all of it
   if (c->hh_min && n) {
@@ -1535,7 +1522,7 @@ int lat_reset(gpuagg_ctx *c, bool full) {
   }
   if (!c->d_lat) {
     if (!c->lat_enabled) return GPUAGG_OK;
-    if (int rc = dev_alloc(c, &c->d_lat, kLatStateWords)) return rc;
+    if (int rc = c->d_lat.alloc(c, kLatStateWords)) return rc;
     full = true;
   }
   if (full) {
@@ -1741,49 +1728,31 @@ int launch_latency(gpuagg_ctx *c, const ColsView &cv, size_t n) {
   a.api = c->d_api;
   a.n_api = (uint32_t)c->api_ips.size();
   a.state = c->d_lat;
-  if ((rc = ensure_buf(c, &c->d_lat_blk_cnt, &c->lat_blk_alloc, a.blocks))) return rc;
-  if (!c->d_lat_blk_max) {
-    const size_t nb = kLatMaxUnits;
-    if ((rc = dev_alloc(c, &c->d_lat_blk_max, nb)) || (rc = dev_alloc(c, &c->d_lat_blk_clk, nb)) ||
-        (rc = dev_alloc(c, &c->d_lat_blk_base, nb)))
-      return rc;
-    if (c->lat_blk_alloc < nb) {  // keep every per-block array the same size
-      dev_free(c, c->d_lat_blk_cnt);
-      c->lat_blk_alloc = 0;
-      if ((rc = ensure_buf(c, &c->d_lat_blk_cnt, &c->lat_blk_alloc, nb))) return rc;
-    }
-  }
+  if ((rc = c->d_lat_blk_cnt.ensure(c, kLatMaxUnits)) || (rc = c->d_lat_blk_max.ensure(c, kLatMaxUnits)) ||
+      (rc = c->d_lat_blk_clk.ensure(c, kLatMaxUnits)) || (rc = c->d_lat_blk_base.ensure(c, kLatMaxUnits)))
+    return rc;
   a.blk_cnt = c->d_lat_blk_cnt;
   a.blk_max = c->d_lat_blk_max;
   a.blk_clk = c->d_lat_blk_clk;
   a.blk_base = c->d_lat_blk_base;
   // events: carried entries + at most one per record
-  const size_t cap = c->lat_carry_bound + n;
-  if (cap > c->lat_ev_alloc) {
-    HIPCHK(c, x_sync(c, c->stream));
-    dev_free(c, c->d_lat_ev);
-    dev_free(c, c->d_lat_hash);
-    dev_free(c, c->d_lat_idx);
-    dev_free(c, c->d_lat_delta);
-    c->lat_ev_alloc = 0;
-    if ((rc = dev_alloc(c, &c->d_lat_ev, cap)) || (rc = dev_alloc(c, &c->d_lat_hash, 2 * cap)) ||
-        (rc = dev_alloc(c, &c->d_lat_idx, 2 * cap)) || (rc = dev_alloc(c, &c->d_lat_delta, 2 * (cap + 1))))
-      return rc;
-    c->lat_ev_alloc = cap;
-  }
+  if ((rc = c->d_lat_ev.ensure(c, c->lat_carry_bound + n))) return rc;
+  const size_t cap = c->d_lat_ev.cap;  // the two halves of the arrays below are this far apart
+  if ((rc = c->d_lat_hash.ensure(c, 2 * cap)) || (rc = c->d_lat_idx.ensure(c, 2 * cap)) ||
+      (rc = c->d_lat_delta.ensure(c, 2 * (cap + 1))))
+    return rc;
   a.limit = c->cfg.latency_limit ? c->cfg.latency_limit : kLatLimit;
-  if (!c->d_lat_max_live && (rc = dev_alloc(c, &c->d_lat_max_live, 1))) return rc;
+  if ((rc = c->d_lat_max_live.ensure(c, 1))) return rc;
   a.delta = c->d_lat_delta;
-  a.live = c->d_lat_delta + c->lat_ev_alloc + 1;
+  a.live = c->d_lat_delta + cap + 1;
   a.max_live = c->d_lat_max_live;
   a.ev = c->d_lat_ev;
   a.hash_in = c->d_lat_hash;
-  a.hash_out = c->d_lat_hash + c->lat_ev_alloc;
+  a.hash_out = c->d_lat_hash + cap;
   a.idx_in = c->d_lat_idx;
-  a.idx_out = c->d_lat_idx + c->lat_ev_alloc;
+  a.idx_out = c->d_lat_idx + cap;
   constexpr size_t kLatReadWords = kLatEvents - kLatPending + 1;
-  if (!c->h_lat_n && hipHostMalloc((void **)&c->h_lat_n, 8 * (kLatReadWords + 1), hipHostMallocDefault) != hipSuccess)
-    return fail(c, GPUAGG_ENOMEM, "hipHostMalloc(%zu)", 8 * (kLatReadWords + 1));
+  if ((rc = c->h_lat_n.ensure(c, kLatReadWords + 1))) return rc;
   a.carry_in = c->d_lat_carry[c->lat_carry_cur];  // copied into the events by the front
   ENQ(c);
   HIPCHK(c, launch_latency_front(a, c->stream));
@@ -1793,41 +1762,22 @@ int launch_latency(gpuagg_ctx *c, const ColsView &cv, size_t n) {
   const uint64_t ne = c->h_lat_n[kLatEvents - kLatPending];
   c->lat_peak_pending = std::max<uint64_t>(c->lat_peak_pending, c->h_lat_n[0]);  // carried into this batch
   // carry-out buffer: at most one entry per event
-  if (ne > c->lat_carry_alloc) {
-    LatEvent *keep = c->d_lat_carry[c->lat_carry_cur];  // read by this batch already (copied)
-    dev_free(c, c->d_lat_carry[c->lat_carry_cur ^ 1]);
-    c->d_lat_carry[c->lat_carry_cur] = nullptr;
-    dev_free(c, keep);
-    c->lat_carry_alloc = 0;
-    if ((rc = dev_alloc(c, &c->d_lat_carry[0], ne)) || (rc = dev_alloc(c, &c->d_lat_carry[1], ne))) return rc;
-    c->lat_carry_alloc = ne;
-  }
+  // (both grow: the one carried in was read by this batch already, copied by the front)
+  if ((rc = c->d_lat_carry[0].ensure(c, ne)) || (rc = c->d_lat_carry[1].ensure(c, ne))) return rc;
   a.carry_out = c->d_lat_carry[c->lat_carry_cur ^ 1];
   size_t tb = 0;
   HIPCHK(c, latency_sort_bytes(ne, &tb));
-  if (tb > c->lat_tmp_alloc) {
-    if (c->d_lat_tmp) hipFree(c->d_lat_tmp);
-    c->d_lat_tmp = nullptr;
-    c->lat_tmp_alloc = 0;
-    HIPCHK(c, hipMalloc(&c->d_lat_tmp, tb));
-    c->lat_tmp_alloc = tb;
-  }
+  if ((rc = c->d_lat_tmp.ensure(c, tb))) return rc;
   // the carried entries' LRU order (by last touch), read by the sequential pass if the
   // capacity binds; they sit at event positions [0, pending)
   const uint64_t pend = c->h_lat_n[0];
   if (pend) {
-    if (pend > c->lat_order_alloc) {
-      dev_free(c, c->d_lat_okeys);
-      dev_free(c, c->d_lat_ovals);
-      c->lat_order_alloc = 0;
-      if ((rc = dev_alloc(c, &c->d_lat_okeys, 2 * pend)) || (rc = dev_alloc(c, &c->d_lat_ovals, 2 * pend))) return rc;
-      c->lat_order_alloc = pend;
-    }
-    HIPCHK(c, latency_carry_order(a.ev, pend, c->d_lat_okeys, c->d_lat_ovals, c->d_lat_tmp, c->lat_tmp_alloc,
+    if ((rc = c->d_lat_okeys.ensure(c, 2 * pend)) || (rc = c->d_lat_ovals.ensure(c, 2 * pend))) return rc;
+    HIPCHK(c, latency_carry_order(a.ev, pend, c->d_lat_okeys, c->d_lat_ovals, c->d_lat_tmp, c->d_lat_tmp.cap,
                                   c->stream));
     a.carry_order = c->d_lat_ovals + pend;
   }
-  HIPCHK(c, launch_latency_check(a, ne, c->d_lat_tmp, c->lat_tmp_alloc, c->lat_enabled, c->stream));
+  HIPCHK(c, launch_latency_check(a, ne, c->d_lat_tmp, c->d_lat_tmp.cap, c->lat_enabled, c->stream));
   // The one decision the host takes -- does the capacity bind in this batch? -- is not
   // waited for here (a second blocking sync per batch undid the async submit).
   // The parallel walk and the finish run guarded on the device (both return at once when
@@ -1895,13 +1845,9 @@ int launch(gpuagg_ctx *c, const ColsView &cv, size_t n) {
     if (c->h_grow_words[kSparseWords] && (rc = settle_sparse(c))) return rc;
   }
   LaunchArgs a{};
-  a.ip_slots = c->d_ip;
-  a.ip_mask = (uint32_t)(c->ip_cap / 2 - 1);  // bucket mask
-  a.ip_pre = c->radix ? c->d_rpre : nullptr;
-  a.ip_blk = c->radix ? c->d_rblk : nullptr;
+  a.ip = ip_table(c);
   a.ip_rpn = c->radix && c->radix_n <= kRadixSmall ? c->radix_n : 0u;
   for (uint32_t j = 0; j < kRadixSmall / 2; ++j) a.ip_rp[j] = c->radix_pfx[j];
-  a.ip_seed = c->ip_seed;
   a.plan = c->plan;
   a.dense_cnt = c->d_dense_cnt;
   a.dense_byt = c->d_dense_byt;
@@ -1997,10 +1943,10 @@ int launch(gpuagg_ctx *c, const ColsView &cv, size_t n) {
              << (4 * g);
     a.sig = sig;
   }
-  if (a.dense_ng && !a.dns_compact && c->ipl_bytes && !spans.empty() &&
-      c->ipl_bytes + kL4ExtraBytes < kLdsBytes) {
+  if (a.dense_ng && !a.dns_compact && c->ipl.bytes && !spans.empty() &&
+      c->ipl.bytes + kL4ExtraBytes < kLdsBytes) {
     // (with no group in LDS every update spills, but the IP probes still stay on-chip)
-    const uint32_t L4 = prefix((kLdsBytes - c->ipl_bytes - kL4ExtraBytes) / 4);
+    const uint32_t L4 = prefix((kLdsBytes - c->ipl.bytes - kL4ExtraBytes) / 4);
     {
       a.tier1 = true;
       a.lds_bins = L4;
@@ -2012,34 +1958,12 @@ int launch(gpuagg_ctx *c, const ColsView &cv, size_t n) {
                  << (4 * g);
         a.sig = sig;
       }
-      a.ipl = c->d_ipl;
-      a.ipl_nb = c->ipl_nb;
-      a.ipl_seed = c->ipl_seed;
-      a.ipl_bytes = c->ipl_bytes;
-      a.ipl_radix = c->ipl_radix;
-      a.ipl_dense = c->ipl_dense;
-      a.ipl_npfx = c->ipl_npfx;
-      for (uint32_t j = 0; j < kIprMaxPfx; ++j) {
-        a.ipl_pfx[j] = c->ipl_pfx[j];
-        a.ipl_dr[j] = c->ipl_dr[j];
-      }
+      a.ipl = c->ipl;
     }
   }
   // remote context on the wide-key path: the LDS image of every pod IP (wide_kernel takes
   // it when it fits next to the hot-key cache; the context never reads the apiserver flag)
-  if (hot && c->remote && !a.tier1 && c->ipl_all_bytes) {
-    a.ipl = c->d_ipl_all;
-    a.ipl_nb = c->ipl_all_nb;
-    a.ipl_seed = c->ipl_all_seed;
-    a.ipl_bytes = c->ipl_all_bytes;
-    a.ipl_radix = c->ipl_all_radix;
-    a.ipl_dense = c->ipl_all_dense;
-    a.ipl_npfx = c->ipl_all_npfx;
-    for (uint32_t j = 0; j < kIprMaxPfx; ++j) {
-      a.ipl_pfx[j] = c->ipl_all_pfx[j];
-      a.ipl_dr[j] = c->ipl_all_dr[j];
-    }
-  }
+  if (hot && c->remote && !a.tier1 && c->ipl_all.bytes) a.ipl = c->ipl_all;
   // one 1024-thread workgroup per CU whenever LDS holds bins or spill counters: with
   // dense bins but no LDS prefix (C5: 100k-pod groups) 4x fewer workgroups mean 4x
   // fewer, longer spill lists for the fold (same 16 waves per CU)
@@ -2076,10 +2000,10 @@ int launch(gpuagg_ctx *c, const ColsView &cv, size_t n) {
     if (a.tier1 && a.lds_bins) {  // per-workgroup copies of the LDS bins, summed after
       a.stage_a_stride = (a.lds_bins + 3u) & ~3u;
       // accumulating copies are summed before their buffer can be reallocated
-      if (c->pend.active && c->pend.a.stage_defer && (size_t)a.blocks * a.stage_a_stride > c->stage_a_alloc &&
+      if (c->pend.active && c->pend.a.stage_defer && (size_t)a.blocks * a.stage_a_stride > c->d_stage_a.cap &&
           (rc = fold_pending_dense(c)))
         return rc;
-      if ((rc = ensure_buf(c, &c->d_stage_a, &c->stage_a_alloc, (size_t)a.blocks * a.stage_a_stride)))
+      if ((rc = c->d_stage_a.ensure(c, (size_t)a.blocks * a.stage_a_stride)))
         return rc;
       a.stage_a = c->d_stage_a;
     }
@@ -2168,8 +2092,8 @@ int launch(gpuagg_ctx *c, const ColsView &cv, size_t n) {
     }
     const Geom g = geom(budget);
     if (g.nwin) {
-      if ((rc = ensure_buf(c, &c->d_spill, &c->spill_alloc, (size_t)a.blocks * g.nwin * g.spill_cap))) return rc;
-      if ((rc = ensure_buf(c, &c->d_spill_count, &c->spill_count_alloc, (size_t)a.blocks * g.nwin))) return rc;
+      if ((rc = c->d_spill.ensure(c, (size_t)a.blocks * g.nwin * g.spill_cap))) return rc;
+      if ((rc = c->d_spill_count.ensure(c, (size_t)a.blocks * g.nwin))) return rc;
       a.spill_cap = g.spill_cap;
       a.spill = c->d_spill;
       a.spill_count = c->d_spill_count;
@@ -2179,17 +2103,16 @@ int launch(gpuagg_ctx *c, const ColsView &cv, size_t n) {
       a.win_blocks = g.win_blocks;
       // fold partials are stored (not atomically added) and summed by a reduce pass
       const size_t nb_stage = (size_t)a.win_blocks << a.win_shift;
-      if ((rc = ensure_buf(c, &c->d_stage_b, &c->stage_b_alloc, nb_stage))) return rc;
+      if ((rc = c->d_stage_b.ensure(c, nb_stage))) return rc;
       a.stage_b = c->d_stage_b;
     }
     a.sp_lists = nullptr;
     a.sp_counts = nullptr;
     a.sp_nwin = 0;
     if (g.sp_nwin) {
-      if ((rc = ensure_buf(c, &c->d_sp_lists, &c->sp_lists_alloc,
-                           (size_t)a.blocks * g.sp_nwin * g.sp_cap * list_words)))
+      if ((rc = c->d_sp_lists.ensure(c, (size_t)a.blocks * g.sp_nwin * g.sp_cap * list_words)))
         return rc;
-      if ((rc = ensure_buf(c, &c->d_sp_counts, &c->sp_counts_alloc, (size_t)a.blocks * g.sp_nwin))) return rc;
+      if ((rc = c->d_sp_counts.ensure(c, (size_t)a.blocks * g.sp_nwin))) return rc;
       a.sp_lists = c->d_sp_lists;
       a.sp_counts = c->d_sp_counts;
       a.sp_nwin = g.sp_nwin;
@@ -2207,7 +2130,7 @@ int launch(gpuagg_ctx *c, const ColsView &cv, size_t n) {
     a.fold_flag = nullptr;
     if (fold_cond && a.sp_lists) {
       if (!c->d_fold_flag) {
-        if ((rc = dev_alloc(c, &c->d_fold_flag, 2))) return rc;
+        if ((rc = c->d_fold_flag.alloc(c, 2))) return rc;
         HIPCHK(c, x_set_async(c, c->d_fold_flag, 0, 8, c->stream));
       }
       a.fold_cond = true;
@@ -2245,8 +2168,8 @@ int launch(gpuagg_ctx *c, const ColsView &cv, size_t n) {
     }
   }
   if (c->sv.overflow && c->plan.ngroups > 0) {
-    if (!c->h_grow_words) HIPCHK(c, x_host_alloc(c, (void **)&c->h_grow_words, (kSparseWords + 1) * 8));
-    if (!c->ovf_event) HIPCHK(c, hipEventCreateWithFlags(&c->ovf_event, hipEventDisableTiming));
+    if ((rc = c->h_grow_words.ensure(c, kSparseWords + 1))) return rc;
+    HIPCHK(c, c->ovf_event.create(hipEventDisableTiming));
     HIPCHK(c, x_copy_async(c, &c->h_grow_words[kSparseWords], c->d_overflow, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipEventRecord(c->ovf_event, c->stream));
     c->ovf_armed = true;
@@ -2268,7 +2191,7 @@ int decode(gpuagg_ctx *c, int kind, const void *dev_raw, size_t n, const OutCols
     return fail(c, GPUAGG_EINVAL, "raw records must be 16-byte aligned");
   if (!out.src_ip || !out.dst_ip || !out.bytes || !out.meta) return fail(c, GPUAGG_EINVAL, "decode: null column");
   if (!c->d_decode_oor) {
-    if (int rc = dev_alloc(c, &c->d_decode_oor, 1)) return rc;
+    if (int rc = c->d_decode_oor.alloc(c, 1)) return rc;
     HIPCHK(c, x_set_async(c, c->d_decode_oor, 0, 8, c->stream));
   }
   if (c->cpu) {
@@ -2277,18 +2200,12 @@ int decode(gpuagg_ctx *c, int kind, const void *dev_raw, size_t n, const OutCols
     c->stats.decoded += n;
     return GPUAGG_OK;
   }
-  std::array<hipEvent_t, 2> ev{};
-  if (c->timing) {
-    for (auto &e : ev) HIPCHK(c, hipEventCreateWithFlags(&e, kTimingEventFlags));
-    HIPCHK(c, hipEventRecord(ev[0], c->stream));
-  }
+  Span sp;
+  if (int rc = span_open(c, sp)) return rc;
   DecodeArgs a{kind, dev_raw, n, out, c->d_decode_oor, c->n_cu, (uint64_t)c->time_offset};
   ENQ(c);
   HIPCHK(c, launch_decode(a, c->stream));
-  if (c->timing) {
-    HIPCHK(c, hipEventRecord(ev[1], c->stream));
-    c->pending_decode.push_back(ev);
-  }
+  if (int rc = span_close(c, sp, c->pending_decode)) return rc;
   c->stats.decoded += n;
   return GPUAGG_OK;
 }
@@ -2296,7 +2213,7 @@ int decode(gpuagg_ctx *c, int kind, const void *dev_raw, size_t n, const OutCols
 // Decodes into staging buffer s's columns and aggregates from there.
 int decode_and_launch(gpuagg_ctx *c, gpuagg_ctx::Staging &s, int kind, const void *dev_raw, size_t n) {
   int rc;
-  uint32_t *const *d = s.cols;
+  const DevBuf<uint32_t> *d = s.cols;
   const bool lat = c->lat_enabled != 0;
   const OutCols out{d[0], d[1], d[2], d[3], (c->plan.need_ports || c->cms_len > 0 || lat) ? d[4] : nullptr,
                     c->plan.need_dns ? d[5] : nullptr, lat ? s.tcp_id : nullptr, lat ? s.time_ns : nullptr};
@@ -2314,15 +2231,16 @@ int gpuagg_create(const gpuagg_config *cfg, gpuagg_ctx **out) {
   if (!cfg || !out) return GPUAGG_EINVAL;
   *out = nullptr;
   if (cfg->abi_version != GPUAGG_ABI_VERSION) return GPUAGG_EINVAL;
-  std::unique_ptr<gpuagg_ctx> c(new gpuagg_ctx());
-  c->cfg = *cfg;
-  c->device = cfg->device;
-  c->remote = cfg->remote_context != 0;
   if (cfg->max_slots == 0 || cfg->max_slots > kMaxSlot + 1) return GPUAGG_EINVAL;
   if (cfg->cms_depth && (cfg->cms_width_log2 < 4 || cfg->cms_width_log2 > 28 || cfg->cms_depth > 16))
     return GPUAGG_EINVAL;
   if (cfg->hll_precision && (cfg->hll_precision < 4 || cfg->hll_precision > 18)) return GPUAGG_EINVAL;
   if (cfg->latency_limit > (1u << 26)) return GPUAGG_EINVAL;
+  // (every return below destroys what the ctx holds by then)
+  std::unique_ptr<gpuagg_ctx, void (*)(gpuagg_ctx *)> c(new gpuagg_ctx(), gpuagg_destroy);
+  c->cfg = *cfg;
+  c->device = cfg->device;
+  c->remote = cfg->remote_context != 0;
   if (cfg->flags & GPUAGG_FLAG_CPU_BACKEND) {
     // host threads instead of a device: the node's CPU share (GPUAGG_CPU_THREADS, else the
     // hardware threads, at most 64)
@@ -2335,7 +2253,7 @@ int gpuagg_create(const gpuagg_config *cfg, gpuagg_ctx **out) {
     c->defer_folds = false;
     if (cfg->cms_depth) {
       c->cms_len = (size_t)cfg->cms_depth << cfg->cms_width_log2;
-      if (dev_alloc(c.get(), &c->d_cms, c->cms_len)) return GPUAGG_ENOMEM;
+      if (c->d_cms.alloc(c.get(), c->cms_len)) return GPUAGG_ENOMEM;
     }
     *out = c.release();
     return GPUAGG_OK;
@@ -2348,45 +2266,29 @@ int gpuagg_create(const gpuagg_config *cfg, gpuagg_ctx **out) {
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) return GPUAGG_EDEVICE;  // built for gfx950 only
   if (hipSetDevice(c->device) != hipSuccess) return GPUAGG_EDEVICE;
   if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess) {
-    gpuagg_destroy(c.release());
+      hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking) != hipSuccess)
     return GPUAGG_EDEVICE;
-  }
-  for (auto &st : c->stg)
-    if (hipEventCreateWithFlags(&st.copied, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&st.released, hipEventDisableTiming) != hipSuccess) {
-      gpuagg_destroy(c.release());
-      return GPUAGG_EDEVICE;
-    }
-  if (hipEventCreateWithFlags(&c->enrich_done, hipEventDisableTiming) != hipSuccess) {
-    gpuagg_destroy(c.release());
-    return GPUAGG_EDEVICE;
-  }
+  for (Event *e : {&c->stg[0].copied, &c->stg[0].released, &c->stg[1].copied, &c->stg[1].released, &c->enrich_done})
+    if (e->create(hipEventDisableTiming) != hipSuccess) return GPUAGG_EDEVICE;
   c->n_cu = (uint32_t)prop.multiProcessorCount;
   c->wide_list_bytes = cfg->wide_list_mib ? (uint64_t)cfg->wide_list_mib << 20
                                           : std::min<uint64_t>(kWideListBytes, (uint64_t)prop.totalGlobalMem / 8);
   c->defer_folds = !(cfg->flags & GPUAGG_FLAG_FOLD_PER_BATCH);
   if (cfg->cms_depth) {
     c->cms_len = (size_t)cfg->cms_depth << cfg->cms_width_log2;
-    if (dev_alloc(c.get(), &c->d_cms, c->cms_len)) {
-      gpuagg_destroy(c.release());
-      return GPUAGG_ENOMEM;
-    }
+    if (c->d_cms.alloc(c.get(), c->cms_len)) return GPUAGG_ENOMEM;
   }
-  if (layout_dense(c.get(), key_cap_for(c.get(), 0), false) || reset_state(c.get())) {
-    gpuagg_destroy(c.release());
-    return GPUAGG_EDEVICE;
-  }
+  if (layout_dense(c.get(), key_cap_for(c.get(), 0), false) || reset_state(c.get())) return GPUAGG_EDEVICE;
   *out = c.release();
   return GPUAGG_OK;
 }
 
 void gpuagg_destroy(gpuagg_ctx *c) {
   if (!c) return;
-  if (!c->cpu) {
+  if (c->stream) {  // (no stream: a device ctx whose create failed before it held anything)
     hipSetDevice(c->device);
     if (c->copy_stream) hipStreamSynchronize(c->copy_stream);
-    if (c->stream) hipStreamSynchronize(c->stream);
+    hipStreamSynchronize(c->stream);
   }
   // feeds over this context release their stagings of it now and refuse further puts
   const std::vector<gpuagg_raw_feed *> feeds = c->feeds;
@@ -2397,78 +2299,15 @@ void gpuagg_destroy(gpuagg_ctx *c) {
     free_batch_cols(c, b);
     delete b;
   }
-  dev_free(c, c->d_ip);
-  dev_free(c, c->d_rpre);
-  dev_free(c, c->d_rblk);
-  dev_free(c, c->d_ipl);
-  dev_free(c, c->d_ipl_all);
-  dev_free(c, c->d_ipc);
-  dev_free(c, c->d_api);
-  dev_free(c, c->d_lat);
-  dev_free(c, c->d_lat_blk_cnt);
-  dev_free(c, c->d_lat_blk_max);
-  dev_free(c, c->d_lat_blk_clk);
-  dev_free(c, c->d_lat_blk_base);
-  dev_free(c, c->d_lat_ev);
-  dev_free(c, c->d_lat_hash);
-  dev_free(c, c->d_lat_idx);
-  dev_free(c, c->d_lat_delta);
-  dev_free(c, c->d_lat_max_live);
-  dev_free(c, c->d_lat_okeys);
-  dev_free(c, c->d_lat_ovals);
-  dev_free(c, c->d_lat_carry[0]);
-  dev_free(c, c->d_lat_carry[1]);
-  if (c->d_lat_tmp) hipFree(c->d_lat_tmp);
-  x_host_free(c, c->h_lat_n);
-  x_host_free(c, c->h_sync_words);
-  dev_free(c, c->d_dense_cnt);
-  dev_free(c, c->d_dense_byt);
-  dev_free(c, c->sv.k0);  // k1, k2, cnt, byt point into the same array
-  dev_free(c, c->sv.dropped);
-  dev_free(c, c->d_counter);
-  dev_free(c, c->d_overflow);
-  x_host_free(c, c->h_grow_words);
-  if (c->ovf_event) hipEventDestroy(c->ovf_event);
-  dev_free(c, c->d_export);
-  delta_drop(c);
-  hh_free(c);
-  dev_free(c, c->d_cms);
-  dev_free(c, c->d_hll);
-  dev_free(c, c->d_spill);
-  dev_free(c, c->d_spill_count);
-  dev_free(c, c->d_stage_a);
-  dev_free(c, c->d_fold_flag);
-  dev_free(c, c->d_enrich);
-  dev_free(c, c->d_stage_b);
-  dev_free(c, c->d_sk_lists);
-  dev_free(c, c->d_sk_counts);
-  dev_free(c, c->d_sp_lists);
-  dev_free(c, c->d_sp_counts);
-  dev_free(c, c->d_hll_lists);
-  dev_free(c, c->d_hll_lists2);
-  dev_free(c, c->d_hll_counts2);
-  dev_free(c, c->d_hll_counts);
-  dev_free(c, c->d_decode_oor);
-  for (auto &st : c->stg) {
-    for (auto &p : st.cols) dev_free(c, p);
-    dev_free(c, st.raw);
-    if (st.copied) hipEventDestroy(st.copied);
-    if (st.released) hipEventDestroy(st.released);
-  }
-  if (c->enrich_done) {
-    hipEventDestroy(c->enrich_done);
-  }
   for (ncclComm_t cm : c->rccl_comms) ncclCommDestroy(cm);
   c->rccl_comms.clear();
   if (c->fold_stream) {
     hipStreamSynchronize(c->fold_stream);
     hipStreamDestroy(c->fold_stream);
   }
-  if (c->fold_fork) hipEventDestroy(c->fold_fork);
-  if (c->fold_join) hipEventDestroy(c->fold_join);
   if (c->copy_stream) hipStreamDestroy(c->copy_stream);
   if (c->stream) hipStreamDestroy(c->stream);
-  delete c;
+  delete c;  // the buffers and events go with their owners
 }
 
 const char *gpuagg_last_error(const gpuagg_ctx *c) { return c ? c->err.c_str() : "null ctx"; }
@@ -2764,13 +2603,11 @@ int gpuagg_slot_intern(gpuagg_ctx *c, const char *ns, const char *pod, const cha
 // (one u16 read per lookup), radix with its row table (two), else the bucketized cuckoo
 // table.  GPUAGG_FLAG_LDS_CUCKOO / GPUAGG_FLAG_ROW_RADIX force the latter forms
 // (diagnostics and tests).
-struct LdsImage {
-  bool radix = false, dense = false;
-  uint32_t nb = 0, seed = 0, npfx = 0;
-  uint32_t pfx[kIprMaxPfx] = {kIprNoPfx, kIprNoPfx, kIprNoPfx, kIprNoPfx}, dr[kIprMaxPfx] = {};
-  std::vector<uint8_t> bytes;
-};
-bool build_lds_image(const std::vector<std::pair<uint32_t, uint32_t>> &ents, uint32_t flags, LdsImage *out) {
+// *out: the image's description (p null, bytes = the image's size); *bytes: the image.
+static bool build_lds_image(const std::vector<std::pair<uint32_t, uint32_t>> &ents, uint32_t flags, IpImage *out,
+                            std::vector<uint8_t> *bytes) {
+  *out = IpImage{};
+  for (auto &p : out->pfx) p = kIprNoPfx;
   if (!(flags & GPUAGG_FLAG_LDS_CUCKOO)) {
     IprdImage id;
     if (!(flags & GPUAGG_FLAG_ROW_RADIX) && iprd_build(ents, &id)) {
@@ -2780,7 +2617,7 @@ bool build_lds_image(const std::vector<std::pair<uint32_t, uint32_t>> &ents, uin
         out->pfx[j] = id.pfx[j];
         out->dr[j] = id.dr[j];
       }
-      out->bytes = std::move(id.bytes);
+      *bytes = std::move(id.bytes);
       return true;
     }
     IprImage ir;
@@ -2788,7 +2625,7 @@ bool build_lds_image(const std::vector<std::pair<uint32_t, uint32_t>> &ents, uin
       out->radix = true;
       out->npfx = ir.npfx;
       for (uint32_t j = 0; j < kIprMaxPfx; ++j) out->pfx[j] = ir.pfx[j];
-      out->bytes = std::move(ir.bytes);
+      *bytes = std::move(ir.bytes);
       return true;
     }
   }
@@ -2796,8 +2633,25 @@ bool build_lds_image(const std::vector<std::pair<uint32_t, uint32_t>> &ents, uin
   if (!ipl_build(ents, &im)) return false;
   out->nb = im.nb;
   out->seed = im.seed;
-  out->bytes = std::move(im.bytes);
+  *bytes = std::move(im.bytes);
   return true;
+}
+
+// Builds the image of `ents` (when `want`) and uploads it into buf: img describes it, or has
+// bytes 0 when there is none (not wanted, switched off, or no form holds the set).
+static int install_lds_image(gpuagg_ctx *c, const std::vector<std::pair<uint32_t, uint32_t>> &ents, bool want,
+                             DevBuf<uint8_t> &buf, IpImage &img) {
+  img.bytes = 0;
+  IpImage im;
+  std::vector<uint8_t> bytes;
+  if (!want || (c->cfg.flags & GPUAGG_FLAG_NO_LDS_IP_TABLE) || !build_lds_image(ents, c->cfg.flags, &im, &bytes))
+    return GPUAGG_OK;
+  if (int rc = buf.ensure(c, bytes.size())) return rc;
+  HIPCHK(c, x_copy(c, buf, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+  im.p = buf;
+  im.bytes = (uint32_t)bytes.size();
+  img = im;
+  return GPUAGG_OK;
 }
 
 int gpuagg_set_endpoints(gpuagg_ctx *c, const uint32_t *ipv4, const int32_t *slot, size_t n,
@@ -2866,9 +2720,8 @@ int gpuagg_set_endpoints(gpuagg_ctx *c, const uint32_t *ipv4, const int32_t *slo
   if (c->slots.size() > c->key_cap && (rc = layout_dense(c, key_cap_for(c, c->slots.size()), true)))
     return rc;
   if (cap != c->ip_cap) {
-    dev_free(c, c->d_ip);
     c->ip_cap = 0;
-    if ((rc = dev_alloc(c, &c->d_ip, cap))) return rc;
+    if ((rc = c->d_ip.alloc(c, cap))) return rc;
   }
   HIPCHK(c, x_copy(c, c->d_ip, tab.data(), cap * 8, hipMemcpyHostToDevice));
   c->ip_cap = cap;
@@ -2894,70 +2747,25 @@ int gpuagg_set_endpoints(gpuagg_ctx *c, const uint32_t *ipv4, const int32_t *slo
         const uint32_t api = (uint32_t)(kv.second >> 53) & 1u;
         blk[((size_t)blocks[kv.first & 0xFFFFu] << 16) | (kv.first >> 16)] = sl | (api << 31);
       }
-      if (!c->d_rpre && (rc = dev_alloc(c, &c->d_rpre, (size_t)1 << 16))) return rc;
-      if ((rc = ensure_buf(c, &c->d_rblk, &c->rblk_alloc, blk.size()))) return rc;
+      if ((rc = c->d_rpre.ensure(c, (size_t)1 << 16))) return rc;
+      if ((rc = c->d_rblk.ensure(c, blk.size()))) return rc;
       HIPCHK(c, x_copy(c, c->d_rpre, pre.data(), pre.size() * 2, hipMemcpyHostToDevice));
       HIPCHK(c, x_copy(c, c->d_rblk, blk.data(), blk.size() * 4, hipMemcpyHostToDevice));
     }
   }
   // LDS image: non-apiserver pods only (local context treats the apiserver pseudo pod
   // like no endpoint), u16 slot ids
-  c->ipl_bytes = 0;
-  if (!(c->cfg.flags & GPUAGG_FLAG_NO_LDS_IP_TABLE)) {
-    std::vector<std::pair<uint32_t, uint32_t>> ents;
-    for (const auto &kv : last)
-      if (!((kv.second >> 53) & 1))
-        ents.emplace_back(kv.first, (uint32_t)((kv.second >> 32) & ((1u << kSlotBits) - 1)));
-    LdsImage im;
-    if (build_lds_image(ents, c->cfg.flags, &im)) {
-      const uint32_t bytes = (uint32_t)im.bytes.size();
-      if (bytes > c->ipl_alloc) {
-        dev_free(c, c->d_ipl);
-        c->ipl_alloc = 0;
-        if ((rc = dev_alloc(c, &c->d_ipl, bytes))) return rc;
-        c->ipl_alloc = bytes;
-      }
-      HIPCHK(c, x_copy(c, c->d_ipl, im.bytes.data(), bytes, hipMemcpyHostToDevice));
-      c->ipl_radix = im.radix;
-      c->ipl_dense = im.dense;
-      c->ipl_nb = im.nb;
-      c->ipl_seed = im.seed;
-      c->ipl_npfx = im.npfx;
-      for (uint32_t j = 0; j < kIprMaxPfx; ++j) {
-        c->ipl_pfx[j] = im.pfx[j];
-        c->ipl_dr[j] = im.dr[j];
-      }
-      c->ipl_bytes = bytes;
-    }
+  const bool every = c->cfg.hll_precision || c->remote;
+  std::vector<std::pair<uint32_t, uint32_t>> ents, ents_all;
+  for (const auto &kv : last) {
+    const auto ent = std::make_pair(kv.first, (uint32_t)((kv.second >> 32) & ((1u << kSlotBits) - 1)));
+    if (!((kv.second >> 53) & 1)) ents.push_back(ent);
+    if (every) ents_all.push_back(ent);
   }
+  if ((rc = install_lds_image(c, ents, true, c->d_ipl, c->ipl))) return rc;
   // LDS image of every pod IP (the apiserver pseudo pod included: it is a source pod for
   // the HLL) for the sketch pass and the remote context's wide_kernel
-  c->ipl_all_bytes = 0;
-  if ((c->cfg.hll_precision || c->remote) && !(c->cfg.flags & GPUAGG_FLAG_NO_LDS_IP_TABLE)) {
-    std::vector<std::pair<uint32_t, uint32_t>> ents;
-    for (const auto &kv : last) ents.emplace_back(kv.first, (uint32_t)((kv.second >> 32) & ((1u << kSlotBits) - 1)));
-    LdsImage im;
-    if (build_lds_image(ents, c->cfg.flags, &im)) {
-      const uint32_t bytes = (uint32_t)im.bytes.size();
-      if (bytes > c->ipl_all_alloc) {
-        dev_free(c, c->d_ipl_all);
-        c->ipl_all_alloc = 0;
-        if ((rc = dev_alloc(c, &c->d_ipl_all, bytes))) return rc;
-        c->ipl_all_alloc = bytes;
-      }
-      HIPCHK(c, x_copy(c, c->d_ipl_all, im.bytes.data(), bytes, hipMemcpyHostToDevice));
-      c->ipl_all_radix = im.radix;
-      c->ipl_all_dense = im.dense;
-      c->ipl_all_nb = im.nb;
-      c->ipl_all_seed = im.seed;
-      c->ipl_all_npfx = im.npfx;
-      for (uint32_t j = 0; j < kIprMaxPfx; ++j) {
-        c->ipl_all_pfx[j] = im.pfx[j];
-        c->ipl_all_dr[j] = im.dr[j];
-      }
-      c->ipl_all_bytes = bytes;
-    }
-  }
+  if ((rc = install_lds_image(c, ents_all, every, c->d_ipl_all, c->ipl_all))) return rc;
   c->ip_seed = seed;
   c->ip_version = version;
   c->installed.clear();
@@ -3090,8 +2898,8 @@ int gpuagg_retire_slots(gpuagg_ctx *c, size_t *n_retired) {
   for (uint32_t s : dead)
     if (s < c->key_cap) dead_dev.push_back(s);
   if (!dead_dev.empty() && (c->dense_len || c->hll_len)) {
-    uint32_t *d = nullptr;
-    if ((rc = dev_alloc(c, &d, dead_dev.size()))) return rc;
+    DevBuf<uint32_t> d;
+    if ((rc = d.alloc(c, dead_dev.size()))) return rc;
     hipError_t e = x_copy_async(c, d, dead_dev.data(), dead_dev.size() * 4, hipMemcpyHostToDevice, c->stream);
     if (c->cpu) {
       if (e == hipSuccess)
@@ -3110,7 +2918,6 @@ int gpuagg_retire_slots(gpuagg_ctx *c, size_t *n_retired) {
                                  c->stream);
     }
     if (e == hipSuccess) e = x_sync(c, c->stream);
-    dev_free(c, d);
     if (e != hipSuccess) return fail(c, GPUAGG_EDEVICE, "retire: %s", hipGetErrorString(e));
   }
   // group-by entries keyed by a dead slot (as source or destination): the table is
@@ -3389,11 +3196,7 @@ int stage_batch(gpuagg_ctx *c, const gpuagg_batch *b, size_t n, gpuagg_ctx::Stag
 
 int enrich_launch(gpuagg_ctx *c, const uint32_t *src, const uint32_t *dst, size_t n, int32_t *os, int32_t *od) {
   EnrichArgs a{};
-  a.ip_slots = c->d_ip;
-  a.ip_mask = (uint32_t)(c->ip_cap / 2 - 1);  // bucket mask
-  a.ip_pre = c->radix ? c->d_rpre : nullptr;
-  a.ip_blk = c->radix ? c->d_rblk : nullptr;
-  a.ip_seed = c->ip_seed;
+  a.ip = ip_table(c);
   a.src = src;
   a.dst = dst;
   a.n = n;
@@ -3423,7 +3226,7 @@ int gpuagg_submit_enrich(gpuagg_ctx *c, gpuagg_batch *b, size_t n, int32_t *src_
     return launch(c, ColsView{b->cols.src_ip, b->cols.dst_ip, b->cols.bytes, b->cols.meta, b->cols.ports,
                               b->cols.dns_id, b->cols.tcp_id, b->cols.time_ns}, n);
   }
-  if ((rc = ensure_buf(c, &c->d_enrich, &c->enrich_alloc, 2 * b->capacity))) return rc;
+  if ((rc = c->d_enrich.ensure(c, 2 * b->capacity))) return rc;
   gpuagg_ctx::Staging *s;
   ColsView cv{};
   if ((rc = stage_batch(c, b, n, &s, &cv))) return rc;
@@ -3458,7 +3261,7 @@ int gpuagg_sync(gpuagg_ctx *c) {
   if ((rc = settle_sparse(c))) return rc;
   // the counters come back on the stream, ahead of its one synchronisation (no blocking
   // copy per counter); the timing events are read when the stats are (gpuagg_get_stats)
-  if (!c->h_sync_words) HIPCHK(c, x_host_alloc(c, (void **)&c->h_sync_words, 16));
+  if ((rc = c->h_sync_words.ensure(c, 2))) return rc;
   uint64_t *w = c->h_sync_words;
   w[0] = w[1] = 0;
   if (c->d_decode_oor) HIPCHK(c, x_copy_async(c, &w[0], c->d_decode_oor, 8, hipMemcpyDeviceToHost, c->stream));
@@ -3527,12 +3330,7 @@ int gx_submit_raw_async(gpuagg_ctx *c, int kind, const void *host_raw, size_t n,
   if (c->cpu) return decode_and_launch(c, c->stg[0], kind, host_raw, n);  // decoded from the caller's memory
   gpuagg_ctx::Staging *s;
   if ((rc = acquire_staging(c, &s))) return rc;
-  if (n * rec > s->raw_alloc) {  // (acquire_staging waited for the kernels reading it)
-    dev_free(c, s->raw);
-    s->raw_alloc = 0;
-    if ((rc = dev_alloc(c, &s->raw, n * rec))) return rc;
-    s->raw_alloc = n * rec;
-  }
+  if ((rc = s->raw.ensure(c, n * rec))) return rc;  // (acquire_staging waited for the kernels reading it)
   HIPCHK(c, x_copy_async(c, s->raw, host_raw, n * rec, hipMemcpyHostToDevice, c->copy_stream));
   return run_staged(c, *s, [&] { return decode_and_launch(c, *s, kind, s->raw, n); }, host_done);
 }
@@ -4219,23 +4017,20 @@ int gpuagg_snapshot_delta(gpuagg_ctx *c, gpuagg_result **out, int *rebased) {
   const bool fresh = !d.active;
   d.active = true;
   // shadows of state that has none yet, zeroed: its first delta is all of it
-  auto zeroed = [&](uint64_t **p, size_t words) -> int {
-    if (int e = dev_alloc(c, p, words)) return e;
-    HIPCHK(c, x_set_async(c, *p, 0, words * 8, c->stream));
+  auto zeroed = [&](DevBuf<uint64_t> &b, size_t words) -> int {
+    if (int e = b.alloc(c, words)) return e;
+    HIPCHK(c, x_set_async(c, b, 0, words * 8, c->stream));
     return GPUAGG_OK;
   };
-  if (!c->cpu && !d.d_ctr) rc = zeroed(&d.d_ctr, 1);
+  if (!c->cpu && !d.d_ctr) rc = zeroed(d.d_ctr, 1);
   if (!rc && c->sparse_slots && !d.d_sparse &&
-      !(rc = zeroed(&d.d_sparse, c->sparse_slots * (c->sv.compact ? 1 : 2))))
+      !(rc = zeroed(d.d_sparse, c->sparse_slots * (c->sv.compact ? 1 : 2))))
     d.slots = c->sparse_slots;
-  if (!rc && c->dense_len && !d.d_cnt && !(rc = zeroed(&d.d_cnt, c->dense_len)) &&
-      !(rc = zeroed(&d.d_byt, c->dense_len)))
+  if (!rc && c->dense_len && !d.d_cnt && !(rc = zeroed(d.d_cnt, c->dense_len)) &&
+      !(rc = zeroed(d.d_byt, c->dense_len)))
     d.bins = c->dense_len;
-  if (!rc && d.bins_out_cap < c->dense_len) {
-    dev_free(c, d.d_bins_out);
-    d.bins_out_cap = 0;
-    if (!(rc = dev_alloc(c, &d.d_bins_out, c->dense_len * kDenseDeltaWords))) d.bins_out_cap = c->dense_len;
-  }
+  if (!rc) rc = d.d_bins_out.ensure(c, c->dense_len * kDenseDeltaWords);
+  const size_t bins_out_cap = d.d_bins_out.cap / kDenseDeltaWords;  // bins
   if (rc) {
     delta_drop(c);
     return rc;
@@ -4257,18 +4052,18 @@ int gpuagg_snapshot_delta(gpuagg_ctx *c, gpuagg_result **out, int *rebased) {
   if (c->dense_len) {
     if (c->cpu) {
       nb = cpu::dense_delta(c->d_dense_cnt, c->d_dense_byt, d.d_cnt, d.d_byt, c->dense_len, d.d_bins_out,
-                            d.bins_out_cap);
+                            bins_out_cap);
     } else {
       hipError_t e = x_set_async(c, d.d_ctr, 0, 8, c->stream);
       ENQ(c);
       if (e == hipSuccess)
         e = launch_dense_delta(c->d_dense_cnt, c->d_dense_byt, d.d_cnt, d.d_byt, c->dense_len, d.d_bins_out,
-                               d.bins_out_cap, d.d_ctr, c->stream);
+                               bins_out_cap, d.d_ctr, c->stream);
       if (e == hipSuccess) e = x_copy_async(c, &nb, d.d_ctr, 8, hipMemcpyDeviceToHost, c->stream);
       if (e == hipSuccess) e = x_sync(c, c->stream);
       if (e != hipSuccess) return failed(fail(c, GPUAGG_EDEVICE, "dense delta scan: %s", hipGetErrorString(e)));
     }
-    if (nb > d.bins_out_cap)
+    if (nb > bins_out_cap)
       return failed(fail(c, GPUAGG_ESTATE, "dense delta scan emitted %llu bins of %zu", (unsigned long long)nb,
                          c->dense_len));
     std::vector<uint64_t> bins(nb * kDenseDeltaWords);
@@ -4908,14 +4703,13 @@ int hh_collect(gpuagg_ctx *c, std::vector<uint32_t> &keys) {
   uint64_t cand = 0, dropped = 0;
   int rc = hh_count(c, &cand, &dropped);
   if (rc || !cand) return rc;
-  uint32_t *d = nullptr;
-  if ((rc = dev_alloc(c, &d, (size_t)cand * 4))) return rc;
+  DevBuf<uint32_t> d;
+  if ((rc = d.alloc(c, (size_t)cand * 4))) return rc;
   keys.resize((size_t)cand * 4);
   ENQ(c);
   hipError_t e = launch_hh_export(hh_table(c), d, (size_t)cand, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(keys.data(), d, keys.size() * 4, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dev_free(c, d);
   if (e != hipSuccess) return fail(c, GPUAGG_EDEVICE, "heavy-hitter export: %s", hipGetErrorString(e));
   return GPUAGG_OK;
 }
@@ -4926,13 +4720,12 @@ int hh_add(gpuagg_ctx *c, const uint32_t *keys4, size_t n) {
     c->hh_cpu.add(keys4, n);
     return GPUAGG_OK;
   }
-  uint32_t *d = nullptr;
-  if (int rc = dev_alloc(c, &d, n * 4)) return rc;
+  DevBuf<uint32_t> d;
+  if (int rc = d.alloc(c, n * 4)) return rc;
   ENQ(c);
   hipError_t e = hipMemcpyAsync(d, keys4, n * 16, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = launch_hh_add(hh_table(c), d, n, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dev_free(c, d);
   if (e != hipSuccess) return fail(c, GPUAGG_EDEVICE, "heavy-hitter insert: %s", hipGetErrorString(e));
   return GPUAGG_OK;
 }
@@ -4966,8 +4759,8 @@ int gpuagg_set_heavy_hitters(gpuagg_ctx *c, uint32_t min_count, uint32_t capacit
   const size_t slots = (size_t)1 << capacity_log2;
   if (c->cpu) {
     c->hh_cpu.capacity = slots;
-  } else if ((rc = dev_alloc(c, &c->d_hh_keys, slots)) || (rc = dev_alloc(c, &c->d_hh_tags, slots)) ||
-             (rc = dev_alloc(c, &c->d_hh_words, kHhWords))) {
+  } else if ((rc = c->d_hh_keys.alloc(c, slots)) || (rc = c->d_hh_tags.alloc(c, slots)) ||
+             (rc = c->d_hh_words.alloc(c, kHhWords))) {
     hh_free(c);
     return rc;
   }
@@ -5012,39 +4805,25 @@ int gpuagg_heavy_hitters(gpuagg_ctx *c, gpuagg_hh_entry *out, size_t k, size_t *
     const size_t slots = (size_t)1 << c->hh_log2;
     size_t tmp_bytes = 0;
     HIPCHK(c, hh_sort_bytes(slots, &tmp_bytes));
-    uint64_t *sort = nullptr;
-    uint8_t *tmp = nullptr;
-    HhEntry *ent = nullptr;
-    auto cleanup = [&] {
-      dev_free(c, sort);
-      dev_free(c, tmp);
-      dev_free(c, ent);
-    };
-    if ((rc = dev_alloc(c, &sort, 2 * slots)) || (rc = dev_alloc(c, &tmp, std::max<size_t>(tmp_bytes, 16)))) {
-      cleanup();
-      return rc;
-    }
+    DevBuf<uint64_t> sort;
+    DevBuf<uint8_t> tmp;
+    DevBuf<HhEntry> ent;
+    if ((rc = sort.alloc(c, 2 * slots)) || (rc = tmp.alloc(c, std::max<size_t>(tmp_bytes, 16)))) return rc;
     uint64_t m = 0;
     ENQ(c);
     hipError_t e = launch_hh_rank(hh_table(c), sort, sort + slots, tmp, tmp_bytes, kk, c->stream);
     if (e == hipSuccess)
       e = hipMemcpyAsync(&m, c->d_hh_words + kHhWordSelect, 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && (m < kk || m > cand)) {
-      cleanup();
+    if (e == hipSuccess && (m < kk || m > cand))
       return fail(c, GPUAGG_EDEVICE, "heavy-hitter ranking selected %llu of %llu candidates for k = %zu",
                   (unsigned long long)m, (unsigned long long)cand, kk);
-    }
-    if (e == hipSuccess && (rc = dev_alloc(c, &ent, (size_t)m))) {
-      cleanup();
-      return rc;
-    }
+    if (e == hipSuccess && (rc = ent.alloc(c, (size_t)m))) return rc;
     top.resize((size_t)m);
     if (e == hipSuccess) e = launch_hh_gather(hh_table(c), sort + slots, (size_t)m, ent, c->stream);
     if (e == hipSuccess)
       e = hipMemcpyAsync(top.data(), ent, (size_t)m * sizeof(HhEntry), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cleanup();
     if (e != hipSuccess) return fail(c, GPUAGG_EDEVICE, "heavy-hitter ranking: %s", hipGetErrorString(e));
     // the device ordered by estimate; the order among equal estimates is the host's
     std::sort(top.begin(), top.end(), hh_entry_before);
@@ -5094,13 +4873,12 @@ int gpuagg_hll_estimate_all(gpuagg_ctx *c, double *out, size_t cap, size_t *n) {
   if (c->cpu) {
     cpu::hll_sums(c->d_hll, p, (uint32_t)rows, sums.data());
   } else {
-    uint64_t *d = nullptr;
-    if ((rc = dev_alloc(c, &d, rows * 3))) return rc;
+    DevBuf<uint64_t> d;
+    if ((rc = d.alloc(c, rows * 3))) return rc;
     ENQ(c);
     hipError_t e = launch_hll_estimate(c->d_hll, p, (uint32_t)rows, d, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(sums.data(), d, rows * 24, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(c, d);
     if (e != hipSuccess) return fail(c, GPUAGG_EDEVICE, "hll_estimate_kernel: %s", hipGetErrorString(e));
   }
   // gpuagg_hll_estimate's estimator on the exact sums: sum 2^-r = lo / 2^32 + hi / 2^64
@@ -5141,7 +4919,7 @@ int gpuagg_state(gpuagg_ctx *c, gpuagg_state_desc *o) {
   o->sparse_len = c->sparse_slots;
   // the latency words a merge sums: both histograms (buckets, count, sum) and no_response
   // (the gaps between them are zero); the clock and the carried requests stay per shard
-  o->latency = c->d_lat ? (uint64_t *)c->d_lat + kLatHist : nullptr;
+  o->latency = c->d_lat ? (uint64_t *)c->d_lat.p + kLatHist : nullptr;
   o->latency_len = c->d_lat ? kLatStateWords - kLatHist : 0;
   return GPUAGG_OK;
 }
@@ -5206,7 +4984,7 @@ int gpuagg_set_sparse_growth(gpuagg_ctx *c, uint32_t max_log2, uint32_t overflow
   // launches name the list, so they are folded before it may be freed
   if ((rc = settle_sparse(c))) return rc;
   HIPCHK(c, x_sync(c, c->stream));  // launches in flight read the list's address
-  if (c->d_overflow && entries != c->grow_entries) dev_free(c, c->d_overflow);
+  if (entries != c->grow_entries) c->d_overflow.reset();
   c->grow_max_log2 = max_log2;
   c->grow_entries = entries;
   return ensure_overflow(c);
@@ -5270,14 +5048,11 @@ int merge_rccl(gpuagg_ctx *const *ctxs, size_t n, const std::vector<int> &devs) 
     total += m[i];
   }
   if ((rc = bind(c0))) return rc;
-  uint64_t *ent = nullptr;
-  if (total && (rc = dev_alloc(c0, &ent, total * kSparseEntryWords))) return rc;
+  DevBuf<uint64_t> ent;
+  if ((rc = ent.alloc(c0, total * kSparseEntryWords))) return rc;
   const bool lat = c0->lat_enabled != 0;
   for (size_t i = 0; i < n; ++i)
-    if (lat && !ctxs[i]->d_lat) {
-      dev_free(c0, ent);
-      return fail(c0, GPUAGG_ESTATE, "merge: ctx %zu has no latency state", i);
-    }
+    if (lat && !ctxs[i]->d_lat) return fail(c0, GPUAGG_ESTATE, "merge: ctx %zu has no latency state", i);
   ncclResult_t r = ncclGroupStart();
   size_t off = 0;
   for (size_t i = 0; i < n && r == ncclSuccess; ++i) {
@@ -5308,19 +5083,11 @@ int merge_rccl(gpuagg_ctx *const *ctxs, size_t n, const std::vector<int> &devs) 
   for (size_t i = 0; i < n; ++i) {  // every stream idle
     hipSetDevice(ctxs[i]->device);
     hipError_t e = hipStreamSynchronize(ctxs[i]->stream);
-    if (e != hipSuccess && r == ncclSuccess) {
-      dev_free(c0, ent);
-      return fail(c0, GPUAGG_EDEVICE, "merge: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess && r == ncclSuccess) return fail(c0, GPUAGG_EDEVICE, "merge: %s", hipGetErrorString(e));
   }
-  if (r != ncclSuccess) {
-    dev_free(c0, ent);
-    return fail(c0, GPUAGG_EDEVICE, "merge over RCCL: %s", nccl_err(r));
-  }
+  if (r != ncclSuccess) return fail(c0, GPUAGG_EDEVICE, "merge over RCCL: %s", nccl_err(r));
   if ((rc = bind(c0))) return rc;
-  rc = total ? gpuagg_sparse_import(c0, ent, total) : GPUAGG_OK;
-  dev_free(c0, ent);
-  if (rc) return rc;
+  if (total && (rc = gpuagg_sparse_import(c0, ent, total))) return rc;
   for (size_t i = 1; i < n; ++i)
     if ((rc = gpuagg_reset(ctxs[i]))) return rc;
   return bind(c0);
@@ -5397,14 +5164,9 @@ int gpuagg_merge(gpuagg_ctx *const *ctxs, size_t n) {
       return merge_rccl(ctxs, n, devs);
   }
   const size_t tmp_bytes = std::max({c0->dense_len * 8, c0->cms_len * 4, c0->hll_len, (size_t)8});
-  uint8_t *tmp = nullptr;
-  if ((rc = dev_alloc(c0, &tmp, tmp_bytes))) return rc;
-  uint64_t *ent = nullptr;
-  size_t ent_cap = 0;
-  auto cleanup = [&] {
-    dev_free(c0, tmp);
-    dev_free(c0, ent);
-  };
+  DevBuf<uint8_t> tmp;
+  if ((rc = tmp.alloc(c0, tmp_bytes))) return rc;
+  DevBuf<uint64_t> ent;
   auto peer = [&](void *dst, const void *src, int src_dev, size_t bytes) -> hipError_t {
     if (host) {
       memcpy(dst, src, bytes);
@@ -5432,30 +5194,22 @@ int gpuagg_merge(gpuagg_ctx *const *ctxs, size_t n) {
     hipError_t e = hipSuccess;
     if (c0->dense_len) {
       if ((e = peer(tmp, ci->d_dense_cnt, ci->device, c0->dense_len * 8)) == hipSuccess)
-        e = add_u64(c0->d_dense_cnt, (const uint64_t *)tmp, c0->dense_len);
+        e = add_u64(c0->d_dense_cnt, (const uint64_t *)tmp.p, c0->dense_len);
       if (e == hipSuccess && (e = peer(tmp, ci->d_dense_byt, ci->device, c0->dense_len * 8)) == hipSuccess)
-        e = add_u64(c0->d_dense_byt, (const uint64_t *)tmp, c0->dense_len);
+        e = add_u64(c0->d_dense_byt, (const uint64_t *)tmp.p, c0->dense_len);
     }
     if (e == hipSuccess && c0->cms_len && (e = peer(tmp, ci->d_cms, ci->device, c0->cms_len * 4)) == hipSuccess)
-      e = add_u32(c0->d_cms, (const uint32_t *)tmp, c0->cms_len);
+      e = add_u32(c0->d_cms, (const uint32_t *)tmp.p, c0->cms_len);
     if (e == hipSuccess && c0->hll_len && (e = peer(tmp, ci->d_hll, ci->device, c0->hll_len)) == hipSuccess)
       e = max_u8(c0->d_hll, tmp, c0->hll_len);
     if (e == hipSuccess) e = x_sync(c0, c0->stream);
-    if (e != hipSuccess) {
-      cleanup();
-      return fail(c0, GPUAGG_EDEVICE, "merge of ctx %zu: %s", i, hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(c0, GPUAGG_EDEVICE, "merge of ctx %zu: %s", i, hipGetErrorString(e));
     if (ci->sparse_slots) {  // group-by entries: exported on ci, inserted-and-added on c0
       if ((rc = bind(ci))) break;
       size_t m = 0;
       if ((rc = export_table(ci, &m))) break;
       if ((rc = bind(c0))) break;
-      if (m > ent_cap) {
-        dev_free(c0, ent);
-        ent_cap = 0;
-        if ((rc = dev_alloc(c0, &ent, m * kSparseEntryWords))) break;
-        ent_cap = m;
-      }
+      if ((rc = ent.ensure(c0, m * kSparseEntryWords))) break;
       if (m) {
         if ((e = peer(ent, ci->d_export, ci->device, m * kSparseEntryWords * 8)) == hipSuccess)
           e = x_sync(c0, c0->stream);
@@ -5478,7 +5232,6 @@ int gpuagg_merge(gpuagg_ctx *const *ctxs, size_t n) {
     if ((rc = gpuagg_reset(ci))) break;
     if ((rc = bind(c0))) break;
   }
-  cleanup();
   if (rc) return rc;
   HIPCHK(c0, x_sync(c0, c0->stream));
   return GPUAGG_OK;
@@ -5490,7 +5243,7 @@ int gpuagg_set_apiserver_ips(gpuagg_ctx *c, const uint32_t *ipv4, size_t n) {
   int rc = bind(c);
   if (rc) return rc;
   HIPCHK(c, x_sync(c, c->stream));  // in-flight batches read the old set
-  if (!c->d_api && (rc = dev_alloc(c, &c->d_api, kLatMaxApi))) return rc;
+  if ((rc = c->d_api.ensure(c, kLatMaxApi))) return rc;
   c->api_ips.assign(ipv4, ipv4 + n);
   if (n) HIPCHK(c, x_copy(c, c->d_api, ipv4, n * 4, hipMemcpyHostToDevice));
   return GPUAGG_OK;
@@ -5507,9 +5260,8 @@ int gpuagg_ipcache_set(gpuagg_ctx *c, const uint32_t *ipv4, const uint32_t *iden
   const size_t cap = img.tab.size();
   HIPCHK(c, x_sync(c, c->stream));  // in-flight decodes read the old image
   if (cap != c->ipc_cap) {
-    dev_free(c, c->d_ipc);
     c->ipc_cap = 0;
-    if ((rc = dev_alloc(c, &c->d_ipc, cap))) return rc;
+    if ((rc = c->d_ipc.alloc(c, cap))) return rc;
     c->ipc_cap = cap;
   }
   HIPCHK(c, x_copy(c, c->d_ipc, img.tab.data(), cap * sizeof(uint4), hipMemcpyHostToDevice));
