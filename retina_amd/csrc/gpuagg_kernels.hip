@@ -3516,18 +3516,20 @@ static hipError_t launch_k(K kern, const KArgs &k, uint32_t blocks, uint32_t thr
 
 // dense_lds_kernel<NG, ., SIG, .> by the launch's vector loads and LDS image form
 template <int NG, uint32_t SIG>
-static hipError_t launch_lds(const LaunchArgs &a, const KArgs &k, uint32_t B, uint32_t T, size_t lds, hipStream_t st) {
-  if (a.vec)
-    return a.ipl.dense   ? launch_k(dense_lds_kernel<NG, true, SIG, 2>, k, B, T, lds, st)
-           : a.ipl.radix ? launch_k(dense_lds_kernel<NG, true, SIG, 1>, k, B, T, lds, st)
-                         : launch_k(dense_lds_kernel<NG, true, SIG, 0>, k, B, T, lds, st);
-  return a.ipl.dense   ? launch_k(dense_lds_kernel<NG, false, SIG, 2>, k, B, T, lds, st)
-         : a.ipl.radix ? launch_k(dense_lds_kernel<NG, false, SIG, 1>, k, B, T, lds, st)
-                       : launch_k(dense_lds_kernel<NG, false, SIG, 0>, k, B, T, lds, st);
+static hipError_t launch_lds(const KernelVariant &v, const KArgs &k, uint32_t B, uint32_t T, size_t lds,
+                             hipStream_t st) {
+  if (v.vec)
+    return v.kip == 2   ? launch_k(dense_lds_kernel<NG, true, SIG, 2>, k, B, T, lds, st)
+           : v.kip == 1 ? launch_k(dense_lds_kernel<NG, true, SIG, 1>, k, B, T, lds, st)
+                        : launch_k(dense_lds_kernel<NG, true, SIG, 0>, k, B, T, lds, st);
+  return v.kip == 2   ? launch_k(dense_lds_kernel<NG, false, SIG, 2>, k, B, T, lds, st)
+         : v.kip == 1 ? launch_k(dense_lds_kernel<NG, false, SIG, 1>, k, B, T, lds, st)
+                      : launch_k(dense_lds_kernel<NG, false, SIG, 0>, k, B, T, lds, st);
 }
 
-hipError_t launch_aggregate(const LaunchArgs &a, hipStream_t st, hipEvent_t between, const char **kernel) {
+hipError_t launch_aggregate(const LaunchArgs &a, hipStream_t st, hipEvent_t between) {
   if (a.n == 0) return hipSuccess;
+  const KernelVariant &v = a.variant;
   KArgs k{};
   k.c = DevCols{a.cols.src_ip, a.cols.dst_ip, a.cols.bytes, a.cols.meta, a.cols.ports, a.cols.dns_id};
   k.n = a.n;
@@ -3561,169 +3563,88 @@ hipError_t launch_aggregate(const LaunchArgs &a, hipStream_t st, hipEvent_t betw
   k.sp_nwin = a.sp_lists ? a.sp_nwin : 0u;
   k.sp_cap = a.sp_cap;
   k.accum = a.accum ? 1u : 0u;
-  k.hot_n = a.hot_n;
+  k.hot_n = v.hot_n;
+  k.door_log2 = v.door_log2;
   k.fold_flag = a.sp_lists ? a.fold_flag : nullptr;
-  // row-mask spill entries need every tcpflags group's 8-bin rows aligned in the windows
-  k.row_masks = a.spill ? 1u : 0u;
-  for (int g = 0; g < a.plan.ngroups; ++g)
-    if (a.plan.g[g].family == FAM_TCPFLAGS && !a.plan.g[g].sparse &&
-        (a.plan.g[g].nsub != 8 || a.plan.g[g].dense_base < a.spill_lo || (a.plan.g[g].dense_base - a.spill_lo) % 8))
-      k.row_masks = 0u;
+  k.row_masks = a.row_masks ? 1u : 0u;
   k.fold_parity = a.fold_parity;
   k.p = a.plan;
-  const bool sketch = a.cms_depth || a.hll_p;
-  size_t lds = a.tier1 ? (size_t)a.ipl.bytes + (size_t)a.lds_bins * 4 + kL4ExtraBytes
-                       : ((size_t)a.lds_bins + kLdsExtraWords) * 8 + (size_t)k.sp_nwin * 4 +
-                             (a.hot_n ? 4 + (size_t)a.hot_n * kHotKeyBytes : 0);
-  // the hot-key cache's doorkeeper bitmap takes what LDS is left (2^13 .. 2^18 bits) on the
-  // wide-key list path, where any key may otherwise claim an entry
-  k.door_log2 = 0;
-  if (!a.tier1 && a.hot_n && k.sp_nwin && !a.sparse.compact)
-    for (uint32_t l = 18; l >= 13; --l)
-      if (lds + ((size_t)1 << (l - 3)) <= kLdsBytes) {
-        k.door_log2 = l;
-        lds += (size_t)1 << (l - 3);
-        break;
-      }
   const uint32_t B = a.blocks, T = a.threads;
-  hipError_t e;
-  // sparse-only plans on the wide-key list path (no dense group, no tcpflags, no sketch,
-  // <= 4 groups): wide_kernel
-  bool wide = !a.tier1 && !a.dense_ng && !sketch && a.vec && a.hot_n && k.sp_nwin && !a.sparse.compact &&
-              a.plan.ngroups >= 1 && a.plan.ngroups <= 4;
-  bool excl = true;
-  for (int g = 0; wide && g < a.plan.ngroups; ++g) {
-    wide = a.plan.g[g].sparse && a.plan.g[g].family != FAM_TCPFLAGS;
-    for (int h = 0; h < g; ++h) excl &= a.plan.g[h].family != a.plan.g[g].family;
+  const size_t lds = v.lds_bytes;
+  static const bool trace = getenv("GPUAGG_TRACE") != nullptr;
+  if (trace) {
+    char name[64];
+    variant_name(v, name, sizeof name);
+    fprintf(stderr, "gpuagg: launch %s L=%u lds=%u ipl_bytes=%u nwin=%u n=%llu\n", name, a.lds_bins, v.lds_bytes,
+            a.ipl.bytes, a.nwin, (unsigned long long)a.n);
   }
-  if (wide) {
-    const bool remote = !a.plan.local, four = a.plan.ngroups > 2;
-    // LDS: (remote context) the image of every pod IP when it fits next to a cache of
-    // >= kWideIplMinHot entries and a 2^kWideIplMinDoor-bit doorkeeper (the cache halves
-    // until it does), counters, cache, then the largest doorkeeper bitmap that fits
-    const size_t ctr = (size_t)((k.sp_nwin + 1) / 2) * 8, img = remote && a.ipl.p ? ((size_t)a.ipl.bytes + 15) & ~15ull : 0;
-    int kip = -1;
-    if (img) {
-      uint32_t hn = k.hot_n;
-      while (hn > kWideIplMinHot && img + ctr + (size_t)hn * kHotKeyBytes + ((size_t)1 << (kWideIplMinDoor - 3)) > kLdsBytes)
-        hn >>= 1;
-      if (img + ctr + (size_t)hn * kHotKeyBytes + ((size_t)1 << (kWideIplMinDoor - 3)) <= kLdsBytes) {
-        kip = a.ipl.dense ? 2 : a.ipl.radix ? 1 : 0;
-        k.hot_n = hn;
-      }
-    }
-    size_t lw = (kip >= 0 ? img : 0) + ctr + (size_t)k.hot_n * kHotKeyBytes;
-    k.door_log2 = 0;
-    for (uint32_t l = 18; l >= 13; --l)
-      if (lw + ((size_t)1 << (l - 3)) <= kLdsBytes) {
-        k.door_log2 = l;
-        lw += (size_t)1 << (l - 3);
-        break;
-      }
-    if (kernel) {
-      static thread_local char wname[64];
-      snprintf(wname, sizeof wname, "wide_kernel<%d, %s, %s, %d>", four ? 4 : 2, remote ? "true" : "false",
-               excl ? "true" : "false", kip);
-      *kernel = wname;
-    }
-#define GA_WIDE(NG, R, X, I) e = launch_k(wide_kernel<NG, R, X, I>, k, B, T, lw, st)
-#define GA_WIDE_IP(NG, X)                \
-  switch (kip) {                          \
+  // every compiled kernel by its template arguments; a variant that names none is refused
+  hipError_t e = hipErrorInvalidValue;
+#define GA_WIDE(NG, R, X, I) e = launch_k(wide_kernel<NG, R, X, I>, k, B, T, lds, st)
+#define GA_WIDE_IP(NG, X)                   \
+  switch (v.kip) {                          \
     case 2: GA_WIDE(NG, true, X, 2); break; \
     case 1: GA_WIDE(NG, true, X, 1); break; \
     case 0: GA_WIDE(NG, true, X, 0); break; \
-    default: GA_WIDE(NG, true, X, -1);     \
+    case -1: GA_WIDE(NG, true, X, -1);      \
   }
-    if (four) {
-      if (remote) { if (excl) { GA_WIDE_IP(4, true) } else { GA_WIDE_IP(4, false) } }
-      else { if (excl) GA_WIDE(4, false, true, -1); else GA_WIDE(4, false, false, -1); }
-    } else {
-      if (remote) { if (excl) { GA_WIDE_IP(2, true) } else { GA_WIDE_IP(2, false) } }
-      else { if (excl) GA_WIDE(2, false, true, -1); else GA_WIDE(2, false, false, -1); }
-    }
+#define GA_WIDE_NG(NG)                                                     \
+  if (v.opt) { if (v.excl) { GA_WIDE_IP(NG, true) } else { GA_WIDE_IP(NG, false) } } \
+  else if (v.kip == -1) { if (v.excl) GA_WIDE(NG, false, true, -1); else GA_WIDE(NG, false, false, -1); }
+#define GA_LOCAL(NG, ...)                                                          \
+  e = v.vec ? launch_k(dense_local_kernel<NG, true, __VA_ARGS__>, k, B, T, lds, st) \
+            : launch_k(dense_local_kernel<NG, false, __VA_ARGS__>, k, B, T, lds, st)
+  switch (v.family) {
+    case KernelFamily::wide:
+      if (v.ng == 4) { GA_WIDE_NG(4) } else if (v.ng == 2) { GA_WIDE_NG(2) }
+      break;
+    case KernelFamily::dense_lds:
+      if (v.sig == 0) {
+        switch (v.ng) {
+          case 1: e = launch_lds<1, 0>(v, k, B, T, lds, st); break;
+          case 2: e = launch_lds<2, 0>(v, k, B, T, lds, st); break;
+          case 4: e = launch_lds<4, 0>(v, k, B, T, lds, st); break;
+          case 8: e = launch_lds<8, 0>(v, k, B, T, lds, st); break;
+        }
+      } else if (v.ng == 2 && v.sig == kSigFwdLdsDropSpill) {
+        e = launch_lds<2, kSigFwdLdsDropSpill>(v, k, B, T, lds, st);
+      } else if (v.ng == 2 && v.sig == kSigFwdLdsDropLds) {
+        e = launch_lds<2, kSigFwdLdsDropLds>(v, k, B, T, lds, st);
+      } else if (v.ng == 1 && v.sig == kSigFwdLds) {
+        e = launch_lds<1, kSigFwdLds>(v, k, B, T, lds, st);
+      }
+      break;
+    case KernelFamily::dense_local:
+      if (v.sig == 0 && !v.staged && !v.opt) {
+        switch (v.ng) {
+          case 1: GA_LOCAL(1, false); break;
+          case 2: GA_LOCAL(2, false); break;
+          case 4: GA_LOCAL(4, false); break;
+          case 8: GA_LOCAL(8, false); break;
+        }
+      } else if (v.opt) {  // with the compact plan's DNS groups (segment lists)
+        const bool plain = v.sig == 0 && !v.staged, c5 = v.ng == 4 && v.sig == kSigC5;
+        if (plain && v.ng == 1) GA_LOCAL(1, true);
+        else if (plain && v.ng == 2) GA_LOCAL(2, true);
+        else if (plain && v.ng == 4) GA_LOCAL(4, true);
+        else if (c5 && !v.staged) GA_LOCAL(4, true, kSigC5);
+        else if (c5) GA_LOCAL(4, true, kSigC5, true);
+        else if (plain && v.ng == 8) GA_LOCAL(8, true);
+      }
+      break;
+    case KernelFamily::aggregate:
+      if (v.vec)
+        e = v.opt ? launch_k(aggregate_kernel<true, true>, k, B, T, lds, st)
+                  : launch_k(aggregate_kernel<true, false>, k, B, T, lds, st);
+      else
+        e = v.opt ? launch_k(aggregate_kernel<false, true>, k, B, T, lds, st)
+                  : launch_k(aggregate_kernel<false, false>, k, B, T, lds, st);
+      break;
+  }
+#undef GA_LOCAL
+#undef GA_WIDE_NG
 #undef GA_WIDE_IP
 #undef GA_WIDE
-    if (e != hipSuccess) return e;
-    if (between && (e = hipEventRecord(between, st)) != hipSuccess) return e;
-    if (a.defer_folds) {  // lists folded later (launch_folds), or when the device says so
-      LaunchArgs r = a;
-      r.spill = nullptr;
-      r.stage_b = nullptr;
-      if (a.stage_defer) r.stage_a = nullptr;
-      if (!a.fold_cond) r.sp_lists = nullptr;
-      return launch_folds(r, st);
-    }
-    return launch_folds(a, st);
-  }
-  int variant = a.tier1 ? 100 + (int)a.dense_ng : (a.dns_compact && a.dense_ng ? 300 : 0) + (int)a.dense_ng;
-  if (variant == 304 && a.sig == kSigC5) variant = 305;
-  size_t lds_used = lds;
-  if (variant == 305 && a.spill && lds + (size_t)a.nwin * (1 + kSpillRing) * 4 <= kLdsBytes) {
-    variant = 306;  // spill appends staged in LDS rings
-    lds_used = lds + (size_t)a.nwin * (1 + kSpillRing) * 4;
-  }
-  if (a.tier1) {
-    if (a.sig == kSigFwdLdsDropSpill) variant = 200;
-    else if (a.sig == kSigFwdLdsDropLds) variant = 201;
-    else if (a.sig == kSigFwdLds) variant = 202;
-  }
-  static const bool trace = getenv("GPUAGG_TRACE") != nullptr;
-  if (trace)
-    fprintf(stderr, "gpuagg: launch variant=%d tier1=%d sig=0x%x ng=%u L=%u ipl_bytes=%u nwin=%u n=%llu\n",
-            variant, (int)a.tier1, a.sig, a.dense_ng, a.lds_bins, a.ipl.bytes, a.nwin,
-            (unsigned long long)a.n);
-  if (kernel) {
-    static thread_local char name[64];
-    if (a.tier1)
-      snprintf(name, sizeof name, "dense_lds_kernel<%u, %s, %uu, %d>",
-               variant >= 200 ? (variant == 202 ? 1u : 2u) : a.dense_ng, a.vec ? "true" : "false",
-               variant >= 200 ? a.sig : 0u, a.ipl.dense ? 2 : a.ipl.radix ? 1 : 0);
-    else if (a.dense_ng)
-      snprintf(name, sizeof name, "dense_local_kernel<%u, %s, %s, %uu%s>", a.dense_ng, a.vec ? "true" : "false",
-               a.dns_compact ? "true" : "false", variant == 305 || variant == 306 ? a.sig : 0u,
-               variant == 306 ? ", true" : "");
-    else
-      snprintf(name, sizeof name, "aggregate_kernel<%s, %s>", a.vec ? "true" : "false", sketch ? "true" : "false");
-    *kernel = name;
-  }
-  switch (variant) {
-    case 101: e = launch_lds<1, 0>(a, k, B, T, lds, st); break;
-    case 102: e = launch_lds<2, 0>(a, k, B, T, lds, st); break;
-    case 104: e = launch_lds<4, 0>(a, k, B, T, lds, st); break;
-    case 108: e = launch_lds<8, 0>(a, k, B, T, lds, st); break;
-    // compile-time specialised signatures (tier1_signature): the common C2 shapes
-    case 200: e = launch_lds<2, kSigFwdLdsDropSpill>(a, k, B, T, lds, st); break;
-    case 201: e = launch_lds<2, kSigFwdLdsDropLds>(a, k, B, T, lds, st); break;
-    case 202: e = launch_lds<1, kSigFwdLds>(a, k, B, T, lds, st); break;
-    case 1: e = a.vec ? launch_k(dense_local_kernel<1, true, false>, k, B, T, lds, st)
-                      : launch_k(dense_local_kernel<1, false, false>, k, B, T, lds, st); break;
-    case 2: e = a.vec ? launch_k(dense_local_kernel<2, true, false>, k, B, T, lds, st)
-                      : launch_k(dense_local_kernel<2, false, false>, k, B, T, lds, st); break;
-    case 4: e = a.vec ? launch_k(dense_local_kernel<4, true, false>, k, B, T, lds, st)
-                      : launch_k(dense_local_kernel<4, false, false>, k, B, T, lds, st); break;
-    case 8: e = a.vec ? launch_k(dense_local_kernel<8, true, false>, k, B, T, lds, st)
-                      : launch_k(dense_local_kernel<8, false, false>, k, B, T, lds, st); break;
-    // with the compact plan's DNS groups (segment lists)
-    case 301: e = a.vec ? launch_k(dense_local_kernel<1, true, true>, k, B, T, lds, st)
-                        : launch_k(dense_local_kernel<1, false, true>, k, B, T, lds, st); break;
-    case 302: e = a.vec ? launch_k(dense_local_kernel<2, true, true>, k, B, T, lds, st)
-                        : launch_k(dense_local_kernel<2, false, true>, k, B, T, lds, st); break;
-    case 304: e = a.vec ? launch_k(dense_local_kernel<4, true, true>, k, B, T, lds, st)
-                        : launch_k(dense_local_kernel<4, false, true>, k, B, T, lds, st); break;
-    case 305: e = a.vec ? launch_k(dense_local_kernel<4, true, true, kSigC5>, k, B, T, lds, st)
-                        : launch_k(dense_local_kernel<4, false, true, kSigC5>, k, B, T, lds, st); break;
-    case 306: e = a.vec ? launch_k(dense_local_kernel<4, true, true, kSigC5, true>, k, B, T, lds_used, st)
-                        : launch_k(dense_local_kernel<4, false, true, kSigC5, true>, k, B, T, lds_used, st); break;
-    case 308: e = a.vec ? launch_k(dense_local_kernel<8, true, true>, k, B, T, lds, st)
-                        : launch_k(dense_local_kernel<8, false, true>, k, B, T, lds, st); break;
-    default:
-      if (a.vec)
-        e = sketch ? launch_k(aggregate_kernel<true, true>, k, B, T, lds, st)
-                   : launch_k(aggregate_kernel<true, false>, k, B, T, lds, st);
-      else
-        e = sketch ? launch_k(aggregate_kernel<false, true>, k, B, T, lds, st)
-                   : launch_k(aggregate_kernel<false, false>, k, B, T, lds, st);
-  }
   if (e != hipSuccess) return e;
   if (between && (e = hipEventRecord(between, st)) != hipSuccess) return e;
   if (a.defer_folds) {  // lists folded later (launch_folds), or when the device says so;

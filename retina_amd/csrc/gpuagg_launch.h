@@ -11,6 +11,7 @@
 #include <stdint.h>
 
 #include "gpuagg_internal.h"
+#include "gpuagg_launch_plan.h"
 #include "ipc_build.h"
 
 namespace gpuagg {
@@ -63,10 +64,10 @@ struct LaunchArgs {
   uint32_t cms_depth, cms_wlog2;
   uint8_t *hll;
   uint32_t hll_p;
-  // geometry (see gpuagg_runtime.cpp: plan_launch)
+  // geometry and kernel (gpuagg_launch_plan.h: plan_shape, plan_batch)
+  KernelVariant variant;
   uint32_t blocks, threads;
   uint64_t chunk;       // records per workgroup, multiple of 4
-  bool vec;             // every column 16-byte aligned: dwordx4 loads
   uint32_t lds_bins;    // dense bins [0, lds_bins) privatised in LDS
   uint64_t dense_len;
   uint32_t *spill;      // per-workgroup spill lists (u32 entries), or null
@@ -74,10 +75,7 @@ struct LaunchArgs {
   uint32_t *spill_count;
   uint32_t win_shift, nwin, win_blocks;  // fold windows of 2^win_shift bins
   uint32_t spill_lo;    // first spilled dense bin (fold windows start here)
-  uint32_t dense_ng;    // 0: generic kernel; 1/2/4/8: dense local-context kernel
-  bool dns_compact;     // dense kernel also inserts the compact plan's DNS keys (segment lists)
-  bool tier1;           // dense kernel with the IP table and u32 bins in LDS
-  uint32_t sig;         // tier-1 group signature (kSig*), 0 when the plan has none
+  bool row_masks;       // spilled tcpflags rows 8-aligned in their windows: one row-mask entry
   IpImage ipl;          // tier-1: the local pods; wide_kernel (remote context): every pod
   // staged flushes (null: flush with global atomics)
   uint32_t *stage_a;        // tier-1: [blocks][stage_a_stride] copies of the u32 LDS bins
@@ -103,7 +101,6 @@ struct LaunchArgs {
   uint32_t *fold_flag;  // [2] u32, zeroed at allocation
   uint32_t fold_parity;
   bool fold_cond;
-  uint32_t hot_n;  // aggregate_kernel's LDS hot-key cache entries (0: none)
 };
 // A second stream for launch_folds: with both compact-key lists and spill lists (C5's
 // plan) the spill-window fold and its reduction run on st2 beside the segment fold on st
@@ -324,10 +321,8 @@ hipError_t launch_hh_gather(const HhTable &t, const uint64_t *sorted, size_t m, 
 hipError_t launch_hll_estimate(const uint8_t *hll, uint32_t p, uint32_t rows, uint64_t *out3, hipStream_t st);
 
 // `between` (may be null) is recorded after aggregate_kernel, before the spill fold.
-// *kernel (may be null) receives the aggregation kernel's signature as rocprofv3 prints it
-// without "void gpuagg::" and the argument list, e.g. "dense_lds_kernel<2, true, 41u>".
-hipError_t launch_aggregate(const LaunchArgs &a, hipStream_t st, hipEvent_t between,
-                            const char **kernel = nullptr);
+// Runs a.variant (variant_name() spells its signature).
+hipError_t launch_aggregate(const LaunchArgs &a, hipStream_t st, hipEvent_t between);
 hipError_t launch_sparse_init(const SparseView &v, size_t slots, hipStream_t st);
 // Clears the dense bins (every endpoint-keyed dense group) and HLL rows (hll may be null)
 // of the ndead slots listed at dead (device u32 array).

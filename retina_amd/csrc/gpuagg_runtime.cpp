@@ -536,6 +536,7 @@ struct gpuagg_ctx {
   struct Pending {
     bool active = false;
     LaunchArgs a{};         // geometry and lists of the launches waiting for their fold
+    ListGeom geom;          // the lists' geometry as planned (gpuagg_launch_plan.h)
     uint64_t budget = 0;    // records per workgroup the lists were sized for
     uint64_t rpb = 0;       // records per workgroup appended so far
   } pend;
@@ -1818,11 +1819,6 @@ int lat_resolve(gpuagg_ctx *c) {
   return GPUAGG_OK;
 }
 
-// Launches whose list folds may wait for one fold_pending (see Pending).
-constexpr uint64_t kDeferLaunches = 64;
-// Spill-only plans defer their folds at launches of at most this many records per workgroup
-// (the Go plugin's 2^22-record batches: 2^14; full-size launches fold per batch, see launch()).
-constexpr uint64_t kSmallLaunchChunk = 1ull << 16;
 // Default device memory for the wide-key segment lists of one ctx (32-byte entries;
 // gpuagg_config.wide_list_mib overrides it): 32 GiB (1024 entries per workgroup and segment at 2^24
 // slots), at most 1/8 of the device.  A list that fills sends its updates to memory-side
@@ -1854,37 +1850,8 @@ int launch(gpuagg_ctx *c, const ColsView &cv, size_t n) {
   a.dense_len = c->dense_len;
   a.sparse = c->sv;
   a.cms = c->d_cms;
-  a.cms_depth = c->cms_len ? c->cfg.cms_depth : 0;
   a.cms_wlog2 = c->cfg.cms_width_log2;
-  a.hll = c->d_hll;
-  a.hll_p = c->hll_len ? c->cfg.hll_precision : 0;
-  // sketches run in their own pass (launch_sketches) so the metric groups keep the
-  // dense fast paths
-  a.cms_depth = 0;
-  a.hll_p = 0;
-  // dense local-context fast path: every group dense, no sketches
-  a.dense_ng = 0;
-  a.dns_compact = false;
-  if (c->plan.local && c->plan.ngroups > 0 && !a.cms_depth && !a.hll_p) {
-    // every group dense, or -- compact plan -- dense and DNS (keys of 64 bits, inserted
-    // through the segment lists by the dense kernel)
-    bool all_dense = true;
-    for (int g = 0; g < c->plan.ngroups; ++g) {
-      const bool dns = c->plan.g[g].family == FAM_DNS_REQ || c->plan.g[g].family == FAM_DNS_RESP;
-      if (c->plan.g[g].sparse && c->sv.compact && dns && c->sparse_slots &&
-          (c->sparse_slots >> c->sv.seg_log2) <= kSparseMaxSegLists && !(c->cfg.flags & GPUAGG_FLAG_DIRECT_SKETCH))
-        a.dns_compact = true;
-      else
-        all_dense &= !c->plan.g[g].sparse;
-    }
-    if (!all_dense) a.dns_compact = false;
-    if (all_dense)
-      for (uint32_t ng : {1u, 2u, 4u, 8u})
-        if ((uint32_t)c->plan.ngroups <= ng) {
-          a.dense_ng = ng;
-          break;
-        }
-  }
+  a.hll = c->d_hll;  // (cms_depth and hll_p stay 0: sketches run in their own pass, launch_sketches)
   if (c->cpu) {  // host threads: every update direct (no LDS, lists or spill)
     a.cols = cv;
     a.n = n;
@@ -1902,195 +1869,74 @@ int launch(gpuagg_ctx *c, const ColsView &cv, size_t n) {
     c->stats.last_kernel = GPUAGG_KERNEL_CPU;
     return GPUAGG_OK;
   }
-  // geometry: one 1024-thread workgroup per CU holding L dense bins in LDS
-  // LDS window: the longest prefix of whole dense groups (hottest first) that fits
-  std::vector<std::pair<uint64_t, uint64_t>> spans;  // (base, bins) of dense groups
-  for (int g = 0; g < c->plan.ngroups; ++g)
-    if (!c->plan.g[g].sparse) spans.emplace_back(c->plan.g[g].dense_base, c->plan.g[g].nbins);
-  std::sort(spans.begin(), spans.end());
-  auto prefix = [&](uint64_t limit) {
-    uint32_t L = 0;
-    for (auto &sp : spans) {
-      if (sp.first != L || sp.first + sp.second > limit) break;
-      L = (uint32_t)(sp.first + sp.second);
-    }
-    return L;
-  };
-  // compact group-by keys (generic kernel) go through per-segment lists whose fill
-  // counters take LDS words from the dense window
-  const bool generic = !a.dense_ng || a.dns_compact;  // kernels that take compact-key lists
-  const uint64_t sp_nwin = c->sparse_slots ? c->sparse_slots >> c->sv.seg_log2 : 0;
-  // wide (192-bit) keys take per-segment lists too when the table has at most 4096
-  // segments of 2^12 slots (sparse_fold_wide_kernel folds one per workgroup)
-  const bool wide_lists = !c->sv.compact && c->sparse_slots && c->sparse_slots <= (1ull << kWideMaxLog2) &&
-                          !(c->cfg.flags & GPUAGG_FLAG_NO_WIDE_LISTS);
-  const bool sp_lists = generic && (c->sv.compact || wide_lists) && sp_nwin && sp_nwin <= kSparseMaxSegLists &&
-                        !(c->cfg.flags & GPUAGG_FLAG_DIRECT_SKETCH);
-  // plans with HBM-table keys (remote context, ip / port options): an LDS cache of the
-  // hot keys per workgroup in front of the table (hot_add in gpuagg_kernels.hip)
-  const bool hot = generic && c->sparse_slots && !c->sv.compact && !(c->cfg.flags & GPUAGG_FLAG_NO_HOT_KEYS);
-  a.hot_n = hot ? kHotKeys : 0u;
-  a.lds_bins = prefix(kLdsMaxBins - (sp_lists ? (uint32_t)(sp_nwin + 1) / 2 : 0u) -
-                      (hot ? kHotKeys * kHotKeyBytes / 8 + 1 : 0u));
-  // tier-1: the LDS IP image plus u32 bins, when at least the hottest group fits
-  a.tier1 = false;
-  a.sig = 0;
-  if (a.dense_ng && a.dns_compact && c->plan.ngroups <= 8) {  // dense_local_kernel's signature
-    uint32_t sig = 0;
-    for (int g = 0; g < c->plan.ngroups; ++g)
-      sig |= sig_group(c->plan.g[g].family, !c->plan.g[g].sparse &&
-                                                c->plan.g[g].dense_base + c->plan.g[g].nbins <= a.lds_bins)
-             << (4 * g);
-    a.sig = sig;
-  }
-  if (a.dense_ng && !a.dns_compact && c->ipl.bytes && !spans.empty() &&
-      c->ipl.bytes + kL4ExtraBytes < kLdsBytes) {
-    // (with no group in LDS every update spills, but the IP probes still stay on-chip)
-    const uint32_t L4 = prefix((kLdsBytes - c->ipl.bytes - kL4ExtraBytes) / 4);
-    {
-      a.tier1 = true;
-      a.lds_bins = L4;
-      a.sig = 0;
-      if (c->plan.ngroups <= 8) {  // groups in layout order, as the kernel indexes them
-        uint32_t sig = 0;
-        for (int g = 0; g < c->plan.ngroups; ++g)
-          sig |= sig_group(c->plan.g[g].family, c->plan.g[g].dense_base + c->plan.g[g].nbins <= L4)
-                 << (4 * g);
-        a.sig = sig;
-      }
-      a.ipl = c->ipl;
-    }
-  }
-  // remote context on the wide-key path: the LDS image of every pod IP (wide_kernel takes
-  // it when it fits next to the hot-key cache; the context never reads the apiserver flag)
-  if (hot && c->remote && !a.tier1 && c->ipl_all.bytes) a.ipl = c->ipl_all;
-  // one 1024-thread workgroup per CU whenever LDS holds bins or spill counters: with
-  // dense bins but no LDS prefix (C5: 100k-pod groups) 4x fewer workgroups mean 4x
-  // fewer, longer spill lists for the fold (same 16 waves per CU)
-  // (the hot-key cache alone fills ~2/3 of the LDS: with 256-thread workgroups a CU would
-  // run 4 waves)
-  const bool wide = a.lds_bins || a.tier1 || c->dense_len > 0 || a.hot_n;
-  a.blocks = wide ? c->n_cu : c->n_cu * 4;
-  a.threads = wide ? 1024 : 256;
+  // the facts the planner decides from (gpuagg_launch_plan.h)
+  auto form = [](const IpImage &im) { return LdsImageFacts{im.bytes, (int8_t)(im.dense ? 2 : im.radix ? 1 : 0)}; };
+  LaunchFacts f{};
+  f.plan = &c->plan;
+  f.sparse_slots = c->sparse_slots;
+  f.compact = c->sv.compact;
+  f.narrow = c->sv.narrow;
+  f.seg_log2 = c->sv.seg_log2;
+  f.dense_len = c->dense_len;
+  f.direct_sketch = c->cfg.flags & GPUAGG_FLAG_DIRECT_SKETCH;
+  f.no_wide_lists = c->cfg.flags & GPUAGG_FLAG_NO_WIDE_LISTS;
+  f.no_hot_keys = c->cfg.flags & GPUAGG_FLAG_NO_HOT_KEYS;
+  f.n_cu = c->n_cu;
+  f.remote = c->remote;
+  f.defer_folds = c->defer_folds;
+  f.wide_list_bytes = c->wide_list_bytes;
+  f.cms = c->cms_len != 0;
+  f.img_local = form(c->ipl);
+  f.img_all = form(c->ipl_all);
+  const LaunchShape s = plan_shape(f);
+  if (s.image != LdsImage::none) a.ipl = s.image == LdsImage::local ? c->ipl : c->ipl_all;
+  a.lds_bins = s.lds_bins;
+  a.blocks = s.blocks;
+  a.threads = s.threads;
+  const uint32_t list_words = list_entry_words(c->sv.compact, c->sv.narrow);
   const uint64_t per_launch = (uint64_t)a.blocks * kMaxRecordsPerBlock;
   for (uint64_t off = 0; c->plan.ngroups > 0 && off < n; off += per_launch) {
     const uint64_t m = std::min<uint64_t>(per_launch, n - off);
     auto sh = [off](const uint32_t *p) { return p ? p + off : nullptr; };
     a.cols = ColsView{sh(cv.src_ip), sh(cv.dst_ip), sh(cv.bytes), sh(cv.meta), sh(cv.ports), sh(cv.dns_id)};
     a.n = m;
-    a.chunk = ((m + a.blocks - 1) / a.blocks + 3) & ~3ULL;
-    if (hot) {
-      // the cache is flushed into the lists once per workgroup and launch: at small batches
-      // (the Go plugin's 1M records: 4k per workgroup) a full 2048-entry cache doubled the
-      // appends, so it is sized ~chunk / 8 (256 .. kHotKeys entries; under Zipf(1.2) the
-      // top 256 keys still carry ~70 % of the updates)
-      uint32_t hn = 256;
-      while (hn < kHotKeys && (uint64_t)hn * 16 <= a.chunk) hn <<= 1;
-      a.hot_n = hn;
+    const uint32_t *cols[6] = {a.cols.src_ip, a.cols.dst_ip, a.cols.bytes, a.cols.meta, a.cols.ports, a.cols.dns_id};
+    BatchFacts in{};
+    in.m = m;
+    for (int j = 0; j < 6; ++j) in.aligned |= (((uintptr_t)cols[j] & 15u) == 0) << j;
+    // accumulating tier-1 copies are summed before their buffer can be reallocated
+    const size_t stage_words = (size_t)s.blocks * s.stage_stride;
+    if (c->pend.active && c->pend.a.stage_defer && stage_words > c->d_stage_a.cap && (rc = fold_pending_dense(c)))
+      return rc;
+    if (c->pend.active) {
+      const LaunchArgs &q = c->pend.a;
+      in.pend.active = true;
+      in.pend.geom = c->pend.geom;
+      in.pend.budget = c->pend.budget;
+      in.pend.rpb = c->pend.rpb;
+      in.pend.blocks = q.blocks;
+      in.pend.lds_bins = q.lds_bins;
+      in.pend.dense_len = q.dense_len;
+      in.pend.same_state = q.dense_cnt == c->d_dense_cnt && q.dense_byt == c->d_dense_byt && q.sparse.k0 == c->sv.k0;
+      in.pend.staged = q.stage_defer && q.stage_a == c->d_stage_a;
+      in.pend.stage_stride = q.stage_a_stride;
     }
-    auto al = [](const uint32_t *p) { return ((uintptr_t)p & 15u) == 0; };
-    a.vec = al(a.cols.src_ip) && al(a.cols.dst_ip) && al(a.cols.bytes) && al(a.cols.meta) &&
-            (!(c->plan.need_ports || c->cms_len) || al(a.cols.ports)) &&
-            (!c->plan.need_dns || al(a.cols.dns_id));
+    const BatchPlan b = plan_batch(f, s, in);
+    if (c->pend.active && !b.accum && (rc = fold_pending_dense(c))) return rc;
+    // the buffers the plan names
+    const ListGeom &g = b.geom;
+    a.variant = b.variant;
+    a.chunk = b.chunk;
+    a.stage_a = nullptr;
+    a.stage_a_stride = s.stage_stride;
+    if (stage_words) {
+      if ((rc = c->d_stage_a.ensure(c, stage_words))) return rc;
+      a.stage_a = c->d_stage_a;
+    }
     a.spill = nullptr;
     a.spill_count = nullptr;
     a.nwin = 0;
     a.stage_b = nullptr;
-    a.stage_a = nullptr;
-    if (a.tier1 && a.lds_bins) {  // per-workgroup copies of the LDS bins, summed after
-      a.stage_a_stride = (a.lds_bins + 3u) & ~3u;
-      // accumulating copies are summed before their buffer can be reallocated
-      if (c->pend.active && c->pend.a.stage_defer && (size_t)a.blocks * a.stage_a_stride > c->d_stage_a.cap &&
-          (rc = fold_pending_dense(c)))
-        return rc;
-      if ((rc = c->d_stage_a.ensure(c, (size_t)a.blocks * a.stage_a_stride)))
-        return rc;
-      a.stage_a = c->d_stage_a;
-    }
-    // List geometry for `budget` records per workgroup: spill lists per fold window for
-    // the bins past the LDS window (overflow falls back to global atomics; a multiple of 4
-    // keeps lists 16-byte aligned), compact-key lists per table segment (at most one
-    // insert per record, hashed evenly: budget / nwin per list + 25 % + 64; a full list
-    // inserts in place, exact).
-    struct Geom {
-      uint32_t nwin = 0, spill_cap = 0, win_blocks = 0, sp_nwin = 0, sp_cap = 0, win_shift = 0;
-      bool operator==(const Geom &o) const {
-        return nwin == o.nwin && spill_cap == o.spill_cap && win_blocks == o.win_blocks && sp_nwin == o.sp_nwin &&
-               sp_cap == o.sp_cap && win_shift == o.win_shift;
-      }
-    };
-    const uint32_t list_words = c->sv.compact ? 1u : (c->sv.narrow ? kWideNarrowWords : kWideEntryWords);
-    auto geom = [&](uint64_t budget) {
-      Geom g;
-      if (c->dense_len > a.lds_bins) {
-        const uint64_t rem = c->dense_len - a.lds_bins;
-        const uint32_t shift = kFoldWindowShift;
-        const uint32_t nwin = (uint32_t)((rem + (1ull << shift) - 1) >> shift);
-        const uint64_t cap = ((2 * budget / nwin + 4096) + 3) & ~3ULL;
-        if (nwin <= kMaxSpillWindows && cap < (1u << 24)) {  // 24-bit index math in the kernels
-          g.nwin = nwin;
-          g.win_shift = shift;
-          g.spill_cap = (uint32_t)cap;
-          g.win_blocks = nwin * std::max<uint32_t>(1u, 2u * c->n_cu / nwin);  // one wave of 2 per CU
-        }
-      }
-      if (sp_lists) {
-        const uint64_t mean = budget / sp_nwin;
-        g.sp_nwin = (uint32_t)sp_nwin;
-        uint64_t cap = (mean + mean / 4 + 64 + 1) & ~1ULL;  // even: 16-byte key pairs
-        if (!c->sv.compact)  // 32- (narrow: 24-) byte entries: wide_list_bytes of lists per ctx
-          cap = std::max<uint64_t>(16, c->wide_list_bytes / (8 * list_words) / ((uint64_t)a.blocks * sp_nwin)) &
-                ~1ULL;
-        g.sp_cap = (uint32_t)cap;
-      }
-      return g;
-    };
-    auto geom_of = [](const LaunchArgs &x) {
-      Geom g;
-      if (x.spill) {
-        g.nwin = x.nwin;
-        g.spill_cap = x.spill_cap;
-        g.win_blocks = x.win_blocks;
-        g.win_shift = x.win_shift;
-      }
-      if (x.sp_lists) {
-        g.sp_nwin = x.sp_nwin;
-        g.sp_cap = x.sp_cap;
-      }
-      return g;
-    };
-    // Deferred folds: while the geometry holds, launches keep appending to the same lists
-    // (their counters start from the stored fill) for up to kDeferLaunches (64) launches' worth
-    // of records per workgroup, and fold_pending folds them once.
-    // Plans with compact-key lists always defer: their fold pays a fixed pass over the
-    // group-by table.  Spill-only plans (C2, C4) defer only small launches (at most
-    // kMaxRecordsPerBlock / kDeferLaunches records per workgroup, e.g. the Go plugin's 2^20
-    // records): there the spill fold's fixed pass over the windows cost more than the
-    // tier-1 kernel itself; at full-size launches appending past earlier launches' entries
-    // measured ~2 % slower in the tier-1 kernel (profiles/round2/r4f_*), so they fold per batch.
-    const bool small_spill = c->dense_len > a.lds_bins && a.chunk <= kSmallLaunchChunk;
-    const bool lists = sp_lists || small_spill;
-    const bool defer = c->defer_folds && lists;
-    // Wide lists (192-bit keys) are folded when the device says so: every launch's fold
-    // skips itself until some list is half full (sparse_fold_wide_kernel), so the host keeps
-    // appending without a record budget -- under skew the LDS hot-key cache absorbs most
-    // updates and a budget that assumes one entry per record folded ~5x too often.
-    const bool fold_cond = defer && sp_lists && !c->sv.compact;
-    uint64_t budget = defer ? std::max<uint64_t>(a.chunk, std::min<uint64_t>(kMaxRecordsPerBlock,
-                                                                             kDeferLaunches * a.chunk))
-                            : a.chunk;
-    if (fold_cond) budget = ~0ull >> 1;
-    bool accum = false;
-    if (c->pend.active) {
-      const LaunchArgs &q = c->pend.a;
-      const Geom pg = geom(c->pend.budget);
-      accum = defer && c->pend.rpb + a.chunk <= c->pend.budget && pg == geom_of(q) && q.blocks == a.blocks &&
-              q.lds_bins == a.lds_bins && q.dense_len == c->dense_len && q.dense_cnt == c->d_dense_cnt &&
-              q.dense_byt == c->d_dense_byt && q.sparse.k0 == c->sv.k0;
-      if (accum) budget = c->pend.budget;
-      else if ((rc = fold_pending_dense(c))) return rc;
-    }
-    const Geom g = geom(budget);
     if (g.nwin) {
       if ((rc = c->d_spill.ensure(c, (size_t)a.blocks * g.nwin * g.spill_cap))) return rc;
       if ((rc = c->d_spill_count.ensure(c, (size_t)a.blocks * g.nwin))) return rc;
@@ -2102,38 +1948,32 @@ int launch(gpuagg_ctx *c, const ColsView &cv, size_t n) {
       a.win_shift = g.win_shift;
       a.win_blocks = g.win_blocks;
       // fold partials are stored (not atomically added) and summed by a reduce pass
-      const size_t nb_stage = (size_t)a.win_blocks << a.win_shift;
-      if ((rc = c->d_stage_b.ensure(c, nb_stage))) return rc;
+      if ((rc = c->d_stage_b.ensure(c, (size_t)a.win_blocks << a.win_shift))) return rc;
       a.stage_b = c->d_stage_b;
     }
     a.sp_lists = nullptr;
     a.sp_counts = nullptr;
     a.sp_nwin = 0;
     if (g.sp_nwin) {
-      if ((rc = c->d_sp_lists.ensure(c, (size_t)a.blocks * g.sp_nwin * g.sp_cap * list_words)))
-        return rc;
+      if ((rc = c->d_sp_lists.ensure(c, (size_t)a.blocks * g.sp_nwin * g.sp_cap * list_words))) return rc;
       if ((rc = c->d_sp_counts.ensure(c, (size_t)a.blocks * g.sp_nwin))) return rc;
       a.sp_lists = c->d_sp_lists;
       a.sp_counts = c->d_sp_counts;
       a.sp_nwin = g.sp_nwin;
       a.sp_cap = g.sp_cap;
     }
-    a.accum = accum;
-    a.defer_folds = defer && (a.spill || a.sp_lists);
-    // small spill-only launches keep the tier-1 copies too: each workgroup continues from
-    // its staged copy and the copies are summed once, by the deferred fold -- the per-launch
-    // stage_reduce_kernel (reading blocks x the LDS bins) was most of such a launch's cost
-    a.stage_defer = a.defer_folds && small_spill && !sp_lists && a.stage_a != nullptr;
-    a.stage_accum = a.stage_defer && accum && c->pend.a.stage_defer && c->pend.a.stage_a == a.stage_a &&
-                    c->pend.a.stage_a_stride == a.stage_a_stride;
-    a.fold_cond = false;
+    a.row_masks = b.row_masks;
+    a.accum = b.accum;
+    a.defer_folds = b.defer;
+    a.stage_defer = b.stage_defer;
+    a.stage_accum = b.stage_accum;
+    a.fold_cond = b.fold_cond;
     a.fold_flag = nullptr;
-    if (fold_cond && a.sp_lists) {
+    if (b.fold_cond) {
       if (!c->d_fold_flag) {
         if ((rc = c->d_fold_flag.alloc(c, 2))) return rc;
         HIPCHK(c, x_set_async(c, c->d_fold_flag, 0, 8, c->stream));
       }
-      a.fold_cond = true;
       a.fold_flag = c->d_fold_flag;
       a.fold_parity = c->fold_parity;
       c->fold_parity ^= 1u;
@@ -2151,12 +1991,14 @@ int launch(gpuagg_ctx *c, const ColsView &cv, size_t n) {
       HIPCHK(c, hipEventCreateWithFlags(&ev[1], kTimingEventFlags));
       HIPCHK(c, hipEventCreateWithFlags(&ev[2], kTimingEventFlags));
     }
-    const char *kname = nullptr;
-    HIPCHK(c, launch_aggregate(a, c->stream, c->timing ? ev[1] : nullptr, &kname));
-    if (kname) c->kernel_name = kname;
+    HIPCHK(c, launch_aggregate(a, c->stream, c->timing ? ev[1] : nullptr));
+    char kname[64];
+    variant_name(a.variant, kname, sizeof kname);
+    c->kernel_name = kname;
     if (a.defer_folds) {
-      c->pend.rpb = (accum ? c->pend.rpb : 0) + a.chunk;
-      c->pend.budget = budget;
+      c->pend.rpb = (b.accum ? c->pend.rpb : 0) + a.chunk;
+      c->pend.budget = b.budget;
+      c->pend.geom = b.geom;
       c->pend.a = a;
       c->pend.active = true;
     }
@@ -2178,8 +2020,8 @@ int launch(gpuagg_ctx *c, const ColsView &cv, size_t n) {
   if (c->lat_enabled && (rc = launch_latency(c, cv, n))) return rc;
   c->stats.records += n;
   c->stats.batches += 1;
-  c->stats.last_kernel = a.tier1 ? GPUAGG_KERNEL_DENSE_LDS_IP
-                         : a.dense_ng ? GPUAGG_KERNEL_DENSE_HBM_IP : GPUAGG_KERNEL_GENERIC;
+  c->stats.last_kernel = s.tier1 ? GPUAGG_KERNEL_DENSE_LDS_IP
+                         : s.dense_ng ? GPUAGG_KERNEL_DENSE_HBM_IP : GPUAGG_KERNEL_GENERIC;
   return GPUAGG_OK;
 }
 
