@@ -316,7 +316,8 @@ struct CompactLists {
 // Insert-or-add into the sparse table. No lane ever waits for another: a lane that
 // meets a slot whose key is still being published moves on, so a key may occupy
 // more than one slot; the host sums duplicates when it renders series.
-// kWait (the overflow list's replay, where the updates of one key arrive together): such a
+// kWait (the overflow list's replay and wide_append's full-list path, where the updates of
+// one key arrive together): such a
 // slot is probed again, at most kImportSpin times, before the lane moves on -- the claimer
 // publishes within a few instructions, so the key keeps one slot.  The lane waits by
 // repeating the probe loop's iteration, not in a loop of its own: a claimer in the same
@@ -397,7 +398,11 @@ __device__ __forceinline__ void wide_append(const DevSparse &s, uint64_t kh, uin
       return;
     }
   }
-  sparse_add(s, k0, k1, k2, c, b);
+  // kWait: when lists fill in many workgroups at once (skew, a small list budget) they add
+  // the same keys here together, often keys the table does not hold yet; a lane that moved on
+  // from a key still being published claimed a slot of its own, and a segment a quarter full
+  // of keys filled up with their copies and lost updates
+  sparse_add<true>(s, k0, k1, k2, c, b);
 }
 
 // Exact add of one (count 1, bytes nb) update into a packed u64 LDS word

@@ -5,16 +5,12 @@ every plan the dense cases run, and at the exact limits that restatement keeps M
 from.  No expected value comes from the planner: they are dense_cases' or literals with their
 arithmetic beside them."""
 
-import os
-import subprocess
-
 import pytest
 
 from retina_amd import workloads as W
 
 from . import dense_cases as D
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from . import host_programs
 
 CUS = 256
 LDS = D.LDS_BYTES                       # 163,840
@@ -28,11 +24,8 @@ NO_BUDGET = (1 << 63) - 1               # wide lists: ~0ull >> 1
 
 
 @pytest.fixture(scope="module")
-def planner(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("plan") / "launch_plan_test")
-    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "retina_amd", "csrc"),
-                    os.path.join(ROOT, "tests", "launch_plan_test.cpp"), "-o", exe], check=True)
-    return exe
+def planner():
+    return host_programs.planner()
 
 
 def grp(fam, nbins=0, base=0, sparse=False, nsub=1, keyed=True):
@@ -52,16 +45,7 @@ def case(groups, **facts):
     return " ".join(list(groups) + ["%s=%d" % (k.replace("__", "."), int(v)) for k, v in facts.items()])
 
 
-def plan(exe, cases):
-    out = subprocess.run([exe], input="\n".join(cases) + "\n", capture_output=True, text=True, check=True).stdout
-    res = []
-    for ln in out.splitlines():
-        head, name = ln.split(" name=")
-        r = {k: int(v) for k, v in (w.split("=") for w in head.split())}
-        r["name"] = name
-        res.append(r)
-    assert len(res) == len(cases)
-    return res
+plan = host_programs.plan
 
 
 def one(exe, groups, **facts):
