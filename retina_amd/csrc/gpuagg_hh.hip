@@ -34,14 +34,15 @@ namespace gpuagg {
 
 namespace {
 
-constexpr uint32_t kHhFull = 0x80000000u, kHhPending = 0x40000000u, kHhDup = 0x20000000u, kHhHash = 0x1FFFFFFFu;
+constexpr uint32_t kHhFull = 0x80000000u, kHhPending = 0x40000000u, kHhDup = 0x20000000u, kHhHash = (1u << kHhTagBits) - 1u;
+static_assert((kHhDup & kHhHash) == 0 && kHhDup == kHhHash + 1u, "the tag word: three state bits above the hash bits");
 // re-reads of a pending slot that may hold this key before probing on (the kFoldSpin
 // convention of the group-by folds: the claimer publishes within a few instructions, the
 // bound keeps every insert finite); the pass path is rare, so the bound is generous
 constexpr uint32_t kHhSpin = 256;
 // per-workgroup LDS set of the keys this workgroup has handed on: 2^11 entries of 20 bytes,
 // kHhLdsProbe slots tried (a key that finds none of them free is simply not remembered)
-constexpr uint32_t kHhLds = 1u << 11, kHhLdsProbe = 4;
+constexpr uint32_t kHhLds = 1u << kHhLdsLog2, kHhLdsProbe = 4;
 
 struct HhK {
   const uint32_t *src, *dst, *ports, *meta;
@@ -54,8 +55,7 @@ struct HhK {
   unsigned long long *words;
 };
 
-__device__ __forceinline__ uint32_t hh_home(uint64_t base, uint32_t mask) { return (uint32_t)(base >> 13) & mask; }
-__device__ __forceinline__ uint32_t hh_hash(uint64_t base) { return (uint32_t)(base >> 35) & kHhHash; }
+// (hh_home, hh_hash, hh_lds_home: gpuagg_launch.h)
 __device__ __forceinline__ bool key_eq(const uint4 &a, const uint4 &b) {
   return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w;
 }
@@ -128,10 +128,9 @@ struct HhLds {
   uint32_t *tag;
   uint4 *key;
 };
-__device__ __forceinline__ uint32_t lds_home(uint64_t base) { return (uint32_t)(base >> 50) & (kHhLds - 1u); }
 // (a converged wave, one key) true: this workgroup has handed the key on already
 __device__ __forceinline__ bool hh_lds_find(const HhLds &L, const uint4 &key, uint64_t base) {
-  const uint32_t want = kHhFull | hh_hash(base), i0 = lds_home(base);
+  const uint32_t want = kHhFull | hh_hash(base), i0 = hh_lds_home(base);
   for (uint32_t q = 0; q < kHhLdsProbe; ++q) {
     const uint32_t i = (i0 + q) & (kHhLds - 1u);
     const uint32_t t = __hip_atomic_load(&L.tag[i], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -141,7 +140,7 @@ __device__ __forceinline__ bool hh_lds_find(const HhLds &L, const uint4 &key, ui
   return false;
 }
 __device__ __forceinline__ void hh_lds_insert(const HhLds &L, const uint4 &key, uint64_t base) {
-  const uint32_t i0 = lds_home(base);
+  const uint32_t i0 = hh_lds_home(base);
   const bool first = (threadIdx.x & 63u) == 0;
   for (uint32_t q = 0; q < kHhLdsProbe; ++q) {
     const uint32_t i = (i0 + q) & (kHhLds - 1u);

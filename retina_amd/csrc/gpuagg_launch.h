@@ -280,6 +280,15 @@ enum : uint32_t {
   kHhWordSelect = 3,   // launch_hh_rank: sorted entries to hand over (the k largest and the ties of the k-th)
   kHhWords = 4
 };
+// The slices of a key's cms_base the readout uses (its low 32 bits and its high 32 are the
+// count-min columns' h1 and h2): the table's home slot, the 29 tag bits of a slot's tag word,
+// and the home in the per-workgroup LDS set of 2^kHhLdsLog2 entries -- the tag's bits 15..25.
+constexpr uint32_t kHhHomeShift = 13;
+constexpr uint32_t kHhTagShift = 35, kHhTagBits = 29;
+constexpr uint32_t kHhLdsShift = 50, kHhLdsLog2 = 11;
+GA_HD uint32_t hh_home(uint64_t base, uint32_t mask) { return (uint32_t)(base >> kHhHomeShift) & mask; }
+GA_HD uint32_t hh_hash(uint64_t base) { return (uint32_t)(base >> kHhTagShift) & ((1u << kHhTagBits) - 1u); }
+GA_HD uint32_t hh_lds_home(uint64_t base) { return (uint32_t)(base >> kHhLdsShift) & ((1u << kHhLdsLog2) - 1u); }
 struct HhTable {
   uint4 *keys;
   uint32_t *tags;

@@ -1,6 +1,7 @@
 """The small host-only C++ programs of the suite (tests/*.cpp that include the engine's headers),
 compiled with g++ once per process into a temporary directory: the launch planner
-(launch_plan_test.cpp; test_launch_plan.py, seglist_cases.py) and key_hash (key_hash_test.cpp)."""
+(launch_plan_test.cpp; test_launch_plan.py, seglist_cases.py), key_hash (key_hash_test.cpp) and the
+heavy-hitter readout's hash slices (hh_hash_test.cpp; hh_cases.py)."""
 
 from __future__ import annotations
 
@@ -12,6 +13,7 @@ import subprocess
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 
 @functools.lru_cache(maxsize=None)
@@ -25,7 +27,9 @@ def _dir() -> str:
 def build(name: str) -> str:
     """tests/<name>.cpp -> the path of its executable."""
     exe = os.path.join(_dir(), name)
+    # (gpuagg_launch.h includes the HIP runtime's header: its host half, nothing is linked)
     subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "retina_amd", "csrc"),
+                    "-D__HIP_PLATFORM_AMD__", "-isystem", os.path.join(ROCM, "include"),
                     os.path.join(ROOT, "tests", name + ".cpp"), "-o", exe], check=True)
     return exe
 

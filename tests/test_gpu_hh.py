@@ -70,3 +70,48 @@ def test_hll_all(be, p):
 
 def test_hll_growth(be):
     H.hll_growth(be)
+
+
+@pytest.mark.parametrize("through", ["add", "records"])
+def test_same_home_chain(be, through):
+    H.same_home_chain(be, through)
+
+
+@pytest.mark.parametrize("through", ["add", "records"])
+@pytest.mark.parametrize("lg", sorted(H.TWINS))
+def test_tag_twins(be, lg, through):
+    H.tag_twins(be, lg, through)
+
+
+def test_lds_six(be):
+    H.lds_six(be)
+
+
+def test_lds_overflow(be):
+    H.lds_overflow(be)
+
+
+def test_zero_estimates(be):
+    H.zero_estimates(be)
+
+
+def test_largest_table(be):
+    H.largest_table(be)
+
+
+def test_direct_rows(be):
+    H.direct_rows(be)
+
+
+def test_capacity_reports(be):
+    H.capacity_reports(be)
+
+
+@pytest.mark.parametrize("p", H.HLL_SWEEP)
+def test_hll_sweep(be, p):
+    H.hll_sweep(be, p)
+
+
+@pytest.mark.parametrize("p", sorted(H.HIGH_RANK))
+def test_hll_high_ranks(be, p):
+    H.hll_high_ranks(be, p)
