@@ -2352,7 +2352,10 @@ __global__ __launch_bounds__(1024) void sketch_stage_kernel(SketchK k) {
                                                     k.ipl_pfx[0], k.ipl_pfx[1], k.ipl_pfx[2], k.ipl_pfx[3],
                                                     k.ipl_dr[0],  k.ipl_dr[1],  k.ipl_dr[2],  k.ipl_dr[3]};
   auto src_slot = [&](uint32_t ip) -> uint32_t {  // slot or >= hll_slots
-    if (kIp) return iv.lookup(ip);
+    if (kIp) {  // kIplNoSlot is below hll_slots once there are more than 0xFFFF rows
+      const uint32_t v = iv.lookup(ip);
+      return v == kIplNoSlot ? 0xFFFFFFFFu : v;
+    }
     const Lk l = k.p ? ip_lookup(k.t, ip) : Lk{-1, 0};
     return l.slot < 0 ? 0xFFFFFFFFu : (uint32_t)l.slot;
   };

@@ -151,11 +151,19 @@ class Geometry:
         return [g for g in self.groups if not g.sparse]
 
 
-def geometry(spec, pods, flags: int = 0) -> Geometry:
+def image_holds(pods, max_slot: Optional[int] = None) -> bool:
+    """ipl_build.h: an LDS image holds u16 slots with 0xFFFF for "no pod", so the largest
+    installed slot id decides -- the pods' count stands for it where slots are never reused."""
+    return (len(pods.endpoints) if max_slot is None else max_slot) < 0xFFFF
+
+
+def geometry(spec, pods, flags: int = 0, n_slots: Optional[int] = None, max_slot: Optional[int] = None) -> Geometry:
     """aggregate() restated: the layout, the tier, the LDS prefix of whole groups, the kernel
-    signature and the spill windows.  Asserts that every residency is decided with MARGIN."""
+    signature and the spill windows.  Asserts that every residency is decided with MARGIN.
+    n_slots: the slots interned (default: one per pod, ids 0 ..); max_slot: the largest
+    installed slot id (`image_holds`)."""
     gs = plan_groups(spec)
-    kc, total = key_cap_for(len(pods.endpoints)), 0
+    kc, total = key_cap_for(len(pods.endpoints) if n_slots is None else n_slots), 0
     for g in gs:
         if not g.sparse:
             g.base, g.nbins = total, (kc if g.keyed else 1) * 2 * g.nsub
@@ -164,7 +172,7 @@ def geometry(spec, pods, flags: int = 0) -> Geometry:
     dns = any(g.sparse for g in gs)
     kip = 0 if flags & CUCKOO else 1 if flags & ROW_RADIX else 2  # build_lds_image
     ipl_lo, ipl_hi = ipl_bytes_range(pods, kip)
-    tier1 = bool(dense) and not dns and not flags & NO_LDS_IP and ipl_hi <= IPL_MAX_BYTES and len(pods.endpoints) < 0xFFFF
+    tier1 = bool(dense) and not dns and not flags & NO_LDS_IP and ipl_hi <= IPL_MAX_BYTES and image_holds(pods, max_slot)
     seg = (1 << SPARSE_CAPACITY_LOG2) >> SPARSE_SEG_LOG2 if dns else 0
     # the limit with the largest and with the smallest image (one number but for kIp 0 / 1)
     lo, hi = [(LDS_BYTES - b - L4_EXTRA_BYTES) // 4 if tier1 else TIER2_MAX_BINS - (seg + 1) // 2 for b in (ipl_hi, ipl_lo)]

@@ -89,7 +89,7 @@ def test_planner_agrees_with_the_dense_cases(planner):
     for pid, spec, pods, flags in dense_case_plans():
         geo = D.geometry(spec, pods, flags)
         image = 0
-        if not flags & D.NO_LDS_IP and len(pods.endpoints) < 0xFFFF:
+        if not flags & D.NO_LDS_IP and D.image_holds(pods):
             image = D.ipl_bytes_range(pods, geo.kip)[1]
             image = image if image <= D.IPL_MAX_BYTES else 0
         groups = [grp(g.fam, g.nbins, g.base, g.sparse, g.nsub, g.keyed) for g in geo.groups]
@@ -120,6 +120,22 @@ def test_planner_agrees_with_the_dense_cases(planner):
             assert r["win_blocks"] == D.fold_partitions(geo, blocks)[0] * geo.nwin and r["win_shift"] == 13, what
         assert r["defer"] == (bool(defer) and bool(geo.nwin or geo.seg_lists)), what
         assert r["kip"] == (geo.kip if geo.tier1 else -1), what
+
+
+def test_image_decided_by_the_largest_installed_slot(planner):
+    """300 pods, 65,600 slots interned: with the largest installed id 0xFFFE build_lds_image still
+    builds the local image and the plan is tier 1; with 0xFFFF (kIplNoSlot) there is none, whatever
+    the number of pods.  145 spill windows either way (65,600 x 18 bins, no group fits LDS)."""
+    pods = D.pods_of(300)
+    assert D.image_holds(pods) and D.image_holds(pods, 0xFFFE) and not D.image_holds(pods, 0xFFFF)
+    for max_slot, tier1 in ((0xFFFE, True), (0xFFFF, False)):
+        geo = D.geometry(D.FWD_DROP, pods, n_slots=65_600, max_slot=max_slot)
+        assert geo.tier1 == tier1 and geo.dense_len == 65_600 * 18 and (geo.L, geo.nwin) == (0, 145)
+        image = D.ipl_bytes_range(pods, geo.kip)[1] if tier1 else 0
+        groups = [grp(g.fam, g.nbins, g.base, g.sparse, g.nsub, g.keyed) for g in geo.groups]
+        r = one(planner, groups, dense_len=geo.dense_len, img_local__bytes=image, img_local__form=geo.kip, m=10_000)
+        assert (r["tier1"], r["lds_bins"], r["nwin"], r["name"]) == (tier1, 0, 145, D.kernel_name(geo)), r
+        assert r["name"] == ("dense_lds_kernel<2, true, 0u, 2>" if tier1 else "dense_local_kernel<2, true, false, 0u>")
 
 
 # ---- the edges the margin hides ----------------------------------------------------------------
