@@ -314,6 +314,16 @@ GA_HD uint32_t iprd_block(uint32_t ip, uint32_t p0, uint32_t p1, uint32_t p2, ui
   return rel < ((d >> 8) & 0x1FFu) ? (d >> 17) + rel : 0u;
 }
 
+// What the launch planners (gpuagg_launch_plan.h, gpuagg_sketch_plan.h) are told of an LDS
+// image, in any of the three forms above, and of a batch's columns.
+struct LdsImageFacts {  // bytes 0: none
+  uint32_t bytes;
+  int8_t form;  // 0 cuckoo, 1 row radix, 2 dense radix (KernelVariant::kip)
+};
+enum : uint32_t {  // the columns that start at a 16-byte boundary (a null column does), in ColsView order
+  kColSrcIp = 1, kColDstIp = 2, kColBytes = 4, kColMeta = 8, kColPorts = 16, kColDnsId = 32
+};
+
 // 32-bit LDS bins of the tier-1 kernel: bytes families pack count:12 | bytes:20 and
 // correct the rare carry / wrap exactly with global atomics; count-only families
 // (tcpflags, tcpretrans) use the whole word (<= 2^20 records per workgroup).

@@ -2312,15 +2312,9 @@ __global__ __launch_bounds__(1024) void sketch_scatter_kernel(SketchK k) {
 // kIp: source lookup 0 HBM table, 1 LDS cuckoo image, 2 LDS radix image, 3 LDS dense radix
 // image.
 // kD: count-min depth fixed at compile time (4), or 0 = k.depth, at most kStageMaxDepth (a
-// record's updates are held in registers, unrolled over that many rows; launch_sketch
-// sends deeper sketches to the unstaged kernel).
-constexpr int kStageMaxDepth = 8;
-__host__ __device__ inline uint32_t stage_words(uint32_t nwin, uint32_t hnsup, uint32_t sbc, uint32_t sbh) {
-  // rc, rb per window + hc, hb per super-window; u16 rings (+ one dummy u32); u32 rings
-  // (+ 64 dummies)
-  return ((2u * (nwin + hnsup) + 3u) & ~3u) + ((nwin * sbc / 2u + 1u + 3u) & ~3u) + hnsup * sbh + 64u;
-}
-
+// record's updates are held in registers, unrolled over that many rows; the planner,
+// gpuagg_sketch_plan.h, sends deeper sketches to the unstaged kernel).  The LDS before the
+// image is laid out as stage_words() of that header counts it.
 template <int kIp, int kD>
 __global__ __launch_bounds__(1024) void sketch_stage_kernel(SketchK k) {
   extern __shared__ __attribute__((aligned(16))) uint32_t sm[];
@@ -2756,179 +2750,113 @@ __global__ __launch_bounds__(1024) void cms_fold_kernel(SketchK k, uint32_t n_li
   }
 }
 
-hipError_t launch_sketch(const SketchArgs &a, hipStream_t st, std::string *kernels, const ForkJoin *fj) {
-  const bool scatter = a.passes != kSketchFolds, folds = a.passes != kSketchScatter;
-  if (a.n == 0 && scatter) return hipSuccess;
-  std::string names;
+// One sketch kernel of 1024-thread workgroups: the dynamic-LDS limit raised past the default
+// 64 KiB when the launch needs it, the launch, its error.
+template <class K, class... A>
+static hipError_t launch_sk(K kern, uint32_t blocks, size_t lds, hipStream_t st, const A &...args) {
+  if (lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(1024), lds, st, args...);
+  return hipGetLastError();
+}
+
+// sketch_stage_kernel<kIp, .> by the count-min depth
+template <int kIp>
+static hipError_t launch_stage(const SketchVariant &v, uint32_t blocks, hipStream_t st, const SketchK &k) {
+  return v.kd == 4 ? launch_sk(sketch_stage_kernel<kIp, 4>, blocks, v.lds_bytes, st, k)
+                   : launch_sk(sketch_stage_kernel<kIp, 0>, blocks, v.lds_bytes, st, k);
+}
+
+hipError_t launch_sketch(const SketchArgs &a, hipStream_t st, const ForkJoin *fj) {
+  const SketchPlan &p = a.plan;
+  const SketchGeom &g = p.geom;
+  const SketchVariant &v = p.variant;
+  if (a.n == 0 && p.scatter) return hipSuccess;
   SketchK k{};
   k.src = a.cols.src_ip;
   k.dst = a.cols.dst_ip;
   k.ports = a.cols.ports;
   k.meta = a.cols.meta;
   k.n = a.n;
-  k.chunk = a.chunk;
+  k.chunk = p.chunk;
   k.t = DevIpTable{a.ip.slots, a.ip.mask, a.ip.seed, a.ip.pre, a.ip.blk, 0u, {}};
   k.cms = a.cms;
   k.depth = a.cms_depth;
   k.wlog2 = a.cms_wlog2;
-  k.wshift = a.win_shift;
-  k.nwin = a.nwin;
-  k.cap = a.cap;
-  k.lists = a.lists;
-  k.counts = a.counts;
+  k.wshift = g.win_shift;
+  k.nwin = g.nwin;
+  k.cap = p.caps.cms;
+  k.lists = a.bufs.lists;
+  k.counts = a.bufs.counts;
   k.hll = (uint32_t *)a.hll;
   k.p = a.hll_p;
-  k.hshift = a.hll_shift;
-  k.hsshift = a.hll_sshift;
-  k.hnsup = a.hll_nsup;
-  k.hnwin = a.hll_nwin;
-  k.hcap = a.hll_cap;
-  k.hlists = a.hll_lists;
-  k.hcounts = a.hll_counts;
-  k.hb2 = a.hll_b2;
-  k.hcap2 = a.hll_cap2;
-  k.hlists2 = a.hll_lists2;
-  k.hcounts2 = a.hll_counts2;
+  k.hshift = g.hll_shift;
+  k.hsshift = g.hll_sshift;
+  k.hnsup = g.hll_nsup;
+  k.hnwin = g.hll_nwin;
+  k.hcap = p.caps.hll;
+  k.hlists = a.bufs.hll_lists;
+  k.hcounts = a.bufs.hll_counts;
+  k.hb2 = g.hll_b2;
+  k.hcap2 = p.caps.hll2;
+  k.hlists2 = a.bufs.hll_lists2;
+  k.hcounts2 = a.bufs.hll_counts2;
   k.hll_slots = a.hll_slots;
-  k.accum = a.accum ? 1u : 0u;
+  k.accum = p.accum ? 1u : 0u;
   hipError_t e;
-  size_t scatter_lds = (size_t)((a.nwin + a.hll_nsup + 3u) & ~3u) * 4;
-  // source lookups in an LDS image of the IP table when it fits next to the counters
-  const bool lds_ip_any = a.ipl.p && a.hll_p && scatter_lds + a.ipl.bytes <= kLdsBytes;
-  const bool lds_ip = lds_ip_any;  // (staged kernel: either image form)
-  if (lds_ip) {
-    k.ipl = a.ipl.p;
-    k.ipl_nb = a.ipl.nb;
-    k.ipl_seed = a.ipl.seed;
-    k.ipl_bytes = a.ipl.bytes;
-    scatter_lds += a.ipl.bytes;
-  }
-  // 16-byte loads need aligned columns and workgroup chunks of whole vectors
-  const bool vec = a.chunk % 4 == 0 && ((uintptr_t)k.src | (uintptr_t)k.dst | (uintptr_t)k.meta |
-                                        (uintptr_t)(k.ports ? k.ports : k.src)) % 16 == 0;
-  // staged scatter: rings sized for a round's mean appends x 1.5 + 64 (the overflow goes
-  // straight to the list), flushed every 4 records per lane, or every 2 when the 4-record
-  // rings do not fit; sources looked up in the radix image when the pod IPs allow one.
-  // Depths above kStageMaxDepth take the unstaged kernel: the staged one would stop at
-  // its unrolled rows and leave the rows above them at zero.
-  bool staged = !scatter;  // a fold-only call launches no scatter
-  if (scatter && vec && a.cms_depth <= (uint32_t)kStageMaxDepth && (!a.cms_depth || a.nwin) &&
-      (!a.hll_p || a.hll_nsup) && (a.nwin || a.hll_nsup)) {
-    const int ip_kind = lds_ip ? (a.ipl.dense ? 3 : a.ipl.radix ? 2 : 1) : 0;
-    if (lds_ip) {
+  if (p.scatter) {
+    if (v.lds_ip) {
+      k.ipl = a.ipl.p;
+      k.ipl_nb = a.ipl.nb;
+      k.ipl_seed = a.ipl.seed;
+      k.ipl_bytes = a.ipl.bytes;
       k.ipl_npfx = a.ipl.npfx;
       for (uint32_t j = 0; j < kIprMaxPfx; ++j) {
         k.ipl_pfx[j] = a.ipl.pfx[j];
         k.ipl_dr[j] = a.ipl.dr[j];
       }
     }
-    const uint32_t img = lds_ip ? a.ipl.bytes : 0u;
-    for (uint32_t round : {4u, 2u}) {
-      const uint64_t per_round = 1024ull * round;
-      auto ring = [](uint64_t mean) {
-        uint32_t r = 64;
-        while (r < mean + mean / 2 + 64) r <<= 1;
-        return r;
-      };
-      const uint32_t sbc = a.nwin ? ring(per_round * a.cms_depth / a.nwin) : 0u;
-      const uint32_t sbh = a.hll_nsup ? ring(per_round / a.hll_nsup) : 0u;
-      const size_t lds = (size_t)stage_words(a.nwin, a.hll_nsup, sbc, sbh) * 4 + img;
-      if (lds > kLdsBytes) continue;
-      k.sbc = sbc;
-      k.sbh = sbh;
-      k.round = round;
-      const bool d4 = a.cms_depth == 4;
-      const void *fn = ip_kind == 3 ? (d4 ? (const void *)sketch_stage_kernel<3, 4> : (const void *)sketch_stage_kernel<3, 0>)
-                     : ip_kind == 2 ? (d4 ? (const void *)sketch_stage_kernel<2, 4> : (const void *)sketch_stage_kernel<2, 0>)
-                     : ip_kind == 1 ? (d4 ? (const void *)sketch_stage_kernel<1, 4> : (const void *)sketch_stage_kernel<1, 0>)
-                                    : (d4 ? (const void *)sketch_stage_kernel<0, 4> : (const void *)sketch_stage_kernel<0, 0>);
-      if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) != hipSuccess) return e;
-      if (ip_kind == 3 && d4) hipLaunchKernelGGL((sketch_stage_kernel<3, 4>), dim3(a.blocks), dim3(1024), lds, st, k);
-      else if (ip_kind == 3) hipLaunchKernelGGL((sketch_stage_kernel<3, 0>), dim3(a.blocks), dim3(1024), lds, st, k);
-      else if (ip_kind == 2 && d4) hipLaunchKernelGGL((sketch_stage_kernel<2, 4>), dim3(a.blocks), dim3(1024), lds, st, k);
-      else if (ip_kind == 2) hipLaunchKernelGGL((sketch_stage_kernel<2, 0>), dim3(a.blocks), dim3(1024), lds, st, k);
-      else if (ip_kind == 1 && d4) hipLaunchKernelGGL((sketch_stage_kernel<1, 4>), dim3(a.blocks), dim3(1024), lds, st, k);
-      else if (ip_kind == 1) hipLaunchKernelGGL((sketch_stage_kernel<1, 0>), dim3(a.blocks), dim3(1024), lds, st, k);
-      else if (d4) hipLaunchKernelGGL((sketch_stage_kernel<0, 4>), dim3(a.blocks), dim3(1024), lds, st, k);
-      else hipLaunchKernelGGL((sketch_stage_kernel<0, 0>), dim3(a.blocks), dim3(1024), lds, st, k);
-      if ((e = hipGetLastError()) != hipSuccess) return e;
-      names = std::string("sketch_stage_kernel<") + std::to_string(ip_kind) + ", " + (d4 ? "4" : "0") + ">";
-      staged = true;
-      break;
-    }
-  }
-  if (!staged) {
-  // the unstaged kernel probes the cuckoo image only: a radix image is looked up in HBM
-  const bool lds_ip = lds_ip_any && !a.ipl.radix && !a.ipl.dense;
-  if (!lds_ip) scatter_lds = (size_t)((a.nwin + a.hll_nsup + 3u) & ~3u) * 4;
-  const void *fn = vec ? (lds_ip ? (const void *)sketch_scatter_kernel<true, true>
-                                 : (const void *)sketch_scatter_kernel<true, false>)
-                       : (lds_ip ? (const void *)sketch_scatter_kernel<false, true>
-                                 : (const void *)sketch_scatter_kernel<false, false>);
-  if (scatter_lds > 64 * 1024 &&
-      (e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)scatter_lds)) != hipSuccess)
-    return e;
-  if (vec && lds_ip) hipLaunchKernelGGL((sketch_scatter_kernel<true, true>), dim3(a.blocks), dim3(1024), scatter_lds, st, k);
-  else if (vec) hipLaunchKernelGGL((sketch_scatter_kernel<true, false>), dim3(a.blocks), dim3(1024), scatter_lds, st, k);
-  else if (lds_ip) hipLaunchKernelGGL((sketch_scatter_kernel<false, true>), dim3(a.blocks), dim3(1024), scatter_lds, st, k);
-  else hipLaunchKernelGGL((sketch_scatter_kernel<false, false>), dim3(a.blocks), dim3(1024), scatter_lds, st, k);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-    names = std::string("sketch_scatter_kernel<") + (vec ? "true" : "false") + ", " + (lds_ip ? "true" : "false") + ">";
-  }  // unstaged
-  if (!folds) {
-    if (kernels) *kernels = names;
-    return hipSuccess;
+    k.sbc = v.sbc;
+    k.sbh = v.sbh;
+    k.round = v.round;
+    const uint32_t B = a.blocks;
+    const size_t lds = v.lds_bytes;
+    if (v.staged)
+      e = v.kip == 3   ? launch_stage<3>(v, B, st, k)
+          : v.kip == 2 ? launch_stage<2>(v, B, st, k)
+          : v.kip == 1 ? launch_stage<1>(v, B, st, k)
+                       : launch_stage<0>(v, B, st, k);
+    else if (v.vec)
+      e = v.lds_ip ? launch_sk(sketch_scatter_kernel<true, true>, B, lds, st, k)
+                   : launch_sk(sketch_scatter_kernel<true, false>, B, lds, st, k);
+    else
+      e = v.lds_ip ? launch_sk(sketch_scatter_kernel<false, true>, B, lds, st, k)
+                   : launch_sk(sketch_scatter_kernel<false, false>, B, lds, st, k);
+    if (e != hipSuccess) return e;
   }
   // the count-min fold beside the HLL chain when both are due (-2 % per C3 step,
   // profiles/round5/exp/r5c3f_*)
-  const bool fork = fj && a.nwin && a.cms_depth && a.hll_nsup && a.hll_p;
-  const hipStream_t cst = fork ? fj->st2 : st;
+  const bool fork = fj && p.fork;
   if (fork) {
     if ((e = hipEventRecord(fj->fork, st)) != hipSuccess || (e = hipStreamWaitEvent(fj->st2, fj->fork, 0)) != hipSuccess)
       return e;
   }
-  if (a.nwin && a.cms_depth) {
-    names += names.empty() ? "cms_fold_kernel" : "+cms_fold_kernel";
-    const size_t lds = (size_t)4 << a.win_shift;
-    if (lds > 64 * 1024 &&
-        (e = hipFuncSetAttribute((const void *)cms_fold_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lds)) != hipSuccess)
+  if (p.fold_cms &&
+      (e = launch_sk(cms_fold_kernel, g.fold_blocks, p.fold.cms_lds, fork ? fj->st2 : st, k, a.blocks)) != hipSuccess)
+    return e;
+  if (p.fold_hll) {
+    k.sbs = p.fold.sbs;
+    k.sbs_every = p.fold.sbs_every;
+    if ((e = launch_sk(hll_split_kernel, g.hll_nsup * g.hll_b2, p.fold.split_lds, st, k, a.blocks)) != hipSuccess)
       return e;
-    hipLaunchKernelGGL(cms_fold_kernel, dim3(a.fold_blocks), dim3(1024), lds, cst, k, a.blocks);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  if (a.hll_nsup && a.hll_p) {
-    names += names.empty() ? "hll_split_kernel+hll_fold_kernel" : "+hll_split_kernel+hll_fold_kernel";
-    // staging rings: a round (4096 entries) over nfine windows, x 2 + 64, when they fit;
-    // larger rings where LDS allows, flushed every few rounds (each flush is a barrier
-    // pair for the workgroup): C3's 128 fine windows take 256-entry rings, every 3 rounds
-    const uint32_t nfine = 1u << (a.hll_sshift - a.hll_shift);
-    const uint32_t per_round = 2 * 4096 / nfine;  // twice the mean appends per window
-    uint32_t R = 64;
-    while (R < per_round + 64) R <<= 1;
-    if ((size_t)(2 + R) * nfine * 4 > kLdsBytes) R = 0;
-    while (R && R < 256 && (size_t)(2 + 2 * R) * nfine * 4 <= kLdsBytes) R <<= 1;
-    k.sbs = R;
-    k.sbs_every = R ? std::max<uint32_t>(1u, (R - 64) / std::max<uint32_t>(1u, per_round)) : 1u;
-    const size_t split_lds = (size_t)(2 + R) * nfine * 4;
-    if ((e = hipFuncSetAttribute((const void *)hll_split_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)split_lds)) != hipSuccess)
-      return e;
-    hipLaunchKernelGGL(hll_split_kernel, dim3(a.hll_nsup * a.hll_b2), dim3(1024), split_lds, st, k, a.blocks);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    const size_t lds = (size_t)1 << (a.hll_p + a.hll_shift);
-    if (lds > 64 * 1024 &&
-        (e = hipFuncSetAttribute((const void *)hll_fold_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)lds)) != hipSuccess)
-      return e;
-    hipLaunchKernelGGL(hll_fold_kernel, dim3(a.hll_nwin), dim3(1024), lds, st, k);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = launch_sk(hll_fold_kernel, g.hll_nwin, p.fold.hll_lds, st, k)) != hipSuccess) return e;
   }
   if (fork) {
     if ((e = hipEventRecord(fj->join, fj->st2)) != hipSuccess || (e = hipStreamWaitEvent(st, fj->join, 0)) != hipSuccess)
       return e;
   }
-  if (kernels) *kernels = names;
   return hipSuccess;
 }
 

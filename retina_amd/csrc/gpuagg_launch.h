@@ -12,6 +12,7 @@
 
 #include "gpuagg_internal.h"
 #include "gpuagg_launch_plan.h"
+#include "gpuagg_sketch_plan.h"
 #include "ipc_build.h"
 
 namespace gpuagg {
@@ -236,39 +237,33 @@ hipError_t launch_latency_walk(const LatArgs &a, size_t n_events, uint32_t enabl
 hipError_t launch_latency_finish(const LatArgs &a, size_t n_events, bool guard, hipStream_t st);
 
 // Sketch pass (count-min by window partition + HLL), after the metric kernels.
-struct SketchArgs {
-  ColsView cols;
-  size_t n;
-  uint64_t chunk;           // records per scatter workgroup
-  uint32_t blocks;          // scatter workgroups (= lists per window)
-  IpTableView ip;
+struct SketchState {  // the count-min rows and the HLL registers
   uint32_t *cms;
   uint32_t cms_depth, cms_wlog2;
-  uint32_t win_shift, nwin, cap;  // windows of 2^win_shift columns; nwin 0: direct atomics
-  uint16_t *lists;
-  uint32_t *counts;
-  uint32_t fold_blocks;     // multiple of nwin
   uint8_t *hll;
   uint32_t hll_p;
-  uint32_t hll_slots;               // slots covered by the registers
-  // HLL two-level bucketing (see SketchK): fine windows of 2^hll_shift pods, super-windows
-  // of 2^hll_sshift pods; hll_nsup 0: direct CAS
-  uint32_t hll_shift, hll_sshift, hll_nsup, hll_nwin, hll_cap;
-  uint32_t *hll_lists, *hll_counts;
-  uint32_t hll_b2, hll_cap2;
-  uint32_t *hll_lists2, *hll_counts2;
-  IpImage ipl;                      // LDS image of every pod IP for the source lookup (bytes 0: none)
-  // which kernels run: the scatter, the folds, or both (kSketchBoth, the default 0); a
-  // scatter with accum appends after the fill earlier scatters stored (deferred folds)
-  uint32_t passes;
-  bool accum;
+  uint32_t hll_slots;  // slots covered by the registers
 };
-constexpr uint32_t kSketchBoth = 0, kSketchScatter = 1, kSketchFolds = 2;
+struct SketchBufs {  // the lists of a plan's geometry and capacities (SketchPlan; layouts: SketchK)
+  uint16_t *lists;
+  uint32_t *counts;
+  uint32_t *hll_lists, *hll_counts;    // level 1
+  uint32_t *hll_lists2, *hll_counts2;  // level 2, needed by the HLL folds alone
+};
+struct SketchArgs : SketchState {
+  SketchBufs bufs;
+  uint32_t blocks;  // scatter workgroups (= lists per window)
+  SketchPlan plan;  // geometry, capacities, which kernels run and their shapes (gpuagg_sketch_plan.h)
+  // the batch (scatter)
+  ColsView cols;
+  size_t n;
+  IpTableView ip;
+  IpImage ipl;  // LDS image of every pod IP for the source lookup, when plan.variant.lds_ip
+};
 struct ForkJoin;
-// *kernels: the pass's kernels in rocprofv3 spelling joined by "+"; fj (may be null): the
-// folds' count-min pass on fj->st2 beside the HLL split + fold on st (disjoint state),
-// joined back into st
-hipError_t launch_sketch(const SketchArgs &a, hipStream_t st, std::string *kernels, const ForkJoin *fj = nullptr);
+// fj (may be null): with plan.fork, the count-min fold on fj->st2 beside the HLL split + fold
+// on st, joined back into st
+hipError_t launch_sketch(const SketchArgs &a, hipStream_t st, const ForkJoin *fj = nullptr);
 
 // Sketch readouts (gpuagg_hh.hip): the heavy-hitter candidate table and the per-pod HLL sums.
 // The table: 2^L slots of a 16-byte key (src_ip, dst_ip, ports, proto) and a u32 tag,

@@ -60,10 +60,6 @@ inline void variant_name(const KernelVariant &v, char *buf, size_t cap) {
 }
 
 // ---- facts ---------------------------------------------------------------------------------
-struct LdsImageFacts {  // an LDS image of an IP table (ipl_build.h); bytes 0: none
-  uint32_t bytes;
-  int8_t form;  // KernelVariant::kip
-};
 struct LaunchFacts {
   const Plan *plan;
   uint64_t sparse_slots;  // group-by table (0: none)
@@ -99,9 +95,6 @@ struct PendingFacts {
   bool same_state = false;  // its counters and table are still the ctx's
   bool staged = false;      // it keeps tier-1 copies (stage_defer) in the buffer this launch would use
   uint32_t stage_stride = 0;
-};
-enum : uint32_t {  // BatchFacts::aligned, in ColsView order
-  kColSrcIp = 1, kColDstIp = 2, kColBytes = 4, kColMeta = 8, kColPorts = 16, kColDnsId = 32
 };
 struct BatchFacts {
   uint64_t m;        // records

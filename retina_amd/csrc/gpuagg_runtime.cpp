@@ -512,7 +512,7 @@ struct gpuagg_ctx {
   Event fold_fork, fold_join;  // fold_stream's
   std::vector<gpuagg_batch *> batches;
   std::string kernel_name;  // aggregation kernel of the last launch (rocprofv3 spelling)
-  std::string sketch_kernel_name;  // kernels of the last sketch pass, joined by "+"
+  std::string sketch_kernel_name;  // scatter kernel of the last sketch pass (rocprofv3 spelling)
 
   // stats / timing
   gpuagg_stats stats{};
@@ -544,7 +544,11 @@ struct gpuagg_ctx {
   // scatter starts from the stored fill) and cms_fold / hll_split / hll_fold run once.
   struct SketchPending {
     bool active = false;
-    SketchArgs s{};       // geometry and lists of the waiting scatters
+    SketchGeom geom;      // the lists' geometry as planned (gpuagg_sketch_plan.h)
+    SketchCaps caps;      // and their capacities
+    SketchState state{};  // the rows and registers they fold into
+    SketchBufs bufs{};
+    uint32_t blocks = 0;  // scatter workgroups
     uint64_t budget = 0;  // records per scatter workgroup the lists were sized for
     uint64_t rpb = 0;     // records per workgroup appended so far
   } sk_pend;
@@ -1288,52 +1292,94 @@ void drain_timing(gpuagg_ctx *c) {
   drain_spans(c->pending_fold, &c->stats.fold_ms);
 }
 
-// Count-min windows: 2^15 columns (128 KiB of LDS in the fold); at most 4096 windows
-// (16 KiB of scatter counters), else every update is a direct global atomic.
-constexpr uint32_t kCmsWindowShift = 15, kCmsMaxWindows = 4096;
-// HLL windows: 2^shift source pods whose registers fit 128 KiB of LDS (entries carry the
-// pod-in-window in 8 bits and the register index in 18, so p <= 17 and shift <= 8)
-constexpr uint32_t kHllWindowLog2Bytes = 17, kHllMaxWindows = 8192;
+// The sketch pass: what the planner (gpuagg_sketch_plan.h) is told of the ctx, of its rows
+// and registers, and of the scatters that wait for their folds.
+static SketchState sketch_state(const gpuagg_ctx *c) {
+  SketchState st{};
+  st.cms = c->d_cms;
+  st.cms_depth = c->cms_len ? c->cfg.cms_depth : 0;
+  st.cms_wlog2 = c->cfg.cms_width_log2;
+  st.hll = c->d_hll;
+  st.hll_p = c->hll_len ? c->cfg.hll_precision : 0;
+  st.hll_slots = st.hll_p ? (uint32_t)(c->hll_len >> st.hll_p) : 0;
+  return st;
+}
+static SketchFacts sketch_facts(const gpuagg_ctx *c, const SketchState &st) {
+  SketchFacts f{};
+  f.cms_depth = st.cms_depth;
+  f.cms_wlog2 = st.cms_wlog2;
+  f.hll_p = st.hll_p;
+  f.hll_slots = st.hll_slots;
+  f.n_cu = c->n_cu;
+  f.direct_sketch = c->cfg.flags & GPUAGG_FLAG_DIRECT_SKETCH;
+  f.defer_folds = c->defer_folds;
+  const IpImage &im = c->ipl_all;
+  f.img_all = LdsImageFacts{im.bytes, (int8_t)(im.dense ? 2 : im.radix ? 1 : 0)};
+  return f;
+}
+static SketchPendingFacts sketch_pending_facts(const gpuagg_ctx *c, const SketchState &st) {
+  const auto &q = c->sk_pend;
+  SketchPendingFacts pf;
+  pf.active = q.active;
+  pf.geom = q.geom;
+  pf.rpb = q.rpb;
+  pf.budget = q.budget;
+  pf.blocks = q.blocks;
+  pf.same_state = q.state.cms == st.cms && q.state.hll == st.hll && q.state.hll_slots == st.hll_slots &&
+                  q.bufs.lists == c->d_sk_lists && q.bufs.hll_lists == c->d_hll_lists;
+  return pf;
+}
+// A fold-only launch of the waiting lists.
+static SketchArgs pending_sketch_args(const gpuagg_ctx *c) {
+  SketchArgs s{};
+  static_cast<SketchState &>(s) = c->sk_pend.state;
+  s.bufs = c->sk_pend.bufs;
+  s.blocks = c->sk_pend.blocks;
+  return s;
+}
 
-// Records per scatter workgroup between deferred sketch folds: 8 full-size C3 launches
-// (2^27 records over 256 workgroups), 256 of the Go plugin's 2^22-record batches; ~15 GB of
-// lists at C3's geometry (d = 4, 256 workgroups), plus the HLL re-bucketing lists at the
-// fold.  Each fold rewrites the whole HLL register array and every count-min row, so fewer,
-// larger folds pay that once per 8 launches instead of once per 2: C3 step 2.41 -> 2.30 ms
-// (2^20 until round 6; 2^21: 2.37; profiles/round6/exp/r6k_c3_sketch_defer_budget_ab.jsonl).
-constexpr uint64_t kSketchDeferRecords = 1ull << 22;
-
-// HLL level-2 (split) lists for `records` scatter entries at most: m / (nsup * b2 * nfine)
-// per list, +25 % + 64 of headroom (a full list applies the update with the global CAS).
-int size_hll_level2(gpuagg_ctx *c, SketchArgs &s, uint64_t records) {
-  const uint64_t nfine = (uint64_t)1 << (s.hll_sshift - s.hll_shift);
-  const uint64_t mean2 = records / ((uint64_t)s.hll_nsup * s.hll_b2 * nfine);
-  const uint64_t cap2 = (mean2 + mean2 / 4 + 64 + 15) & ~15ULL;
-  const size_t n2 = (size_t)s.hll_nsup * s.hll_b2 * nfine;
+// The buffers of a plan's lists: level 1 for the scatter, level 2 when the HLL folds run.
+static int ensure_sketch_lists(gpuagg_ctx *c, const SketchPlan &p, uint32_t blocks, SketchBufs &b) {
+  const SketchGeom &g = p.geom;
   int rc;
-  if ((rc = c->d_hll_lists2.ensure(c, n2 * cap2))) return rc;
-  if ((rc = c->d_hll_counts2.ensure(c, n2))) return rc;
-  s.hll_cap2 = (uint32_t)cap2;
-  s.hll_lists2 = c->d_hll_lists2;
-  s.hll_counts2 = c->d_hll_counts2;
+  if (p.scatter && g.nwin) {
+    if ((rc = c->d_sk_lists.ensure(c, (size_t)blocks * g.nwin * p.caps.cms))) return rc;
+    if ((rc = c->d_sk_counts.ensure(c, (size_t)blocks * g.nwin))) return rc;
+    b.lists = c->d_sk_lists;
+    b.counts = c->d_sk_counts;
+  }
+  if (p.scatter && g.hll_nsup) {
+    if ((rc = c->d_hll_lists.ensure(c, (size_t)blocks * g.hll_nsup * p.caps.hll))) return rc;
+    if ((rc = c->d_hll_counts.ensure(c, (size_t)blocks * g.hll_nsup))) return rc;
+    b.hll_lists = c->d_hll_lists;
+    b.hll_counts = c->d_hll_counts;
+  }
+  if (p.fold_hll) {
+    if ((rc = c->d_hll_lists2.ensure(c, g.hll_lists2() * p.caps.hll2))) return rc;
+    if ((rc = c->d_hll_counts2.ensure(c, g.hll_lists2()))) return rc;
+    b.hll_lists2 = c->d_hll_lists2;
+    b.hll_counts2 = c->d_hll_counts2;
+  }
   return GPUAGG_OK;
 }
 
 // The deferred sketch scatters' lists folded into the count-min rows and HLL registers.
 int fold_pending_sketch(gpuagg_ctx *c) {
-  if (!c->sk_pend.active) return GPUAGG_OK;
-  c->sk_pend.active = false;
-  SketchArgs s = c->sk_pend.s;
-  s.passes = kSketchFolds;
-  s.accum = false;
+  auto &q = c->sk_pend;
+  if (!q.active) return GPUAGG_OK;
+  q.active = false;
+  SketchArgs s = pending_sketch_args(c);
+  SketchCaps caps = q.caps;
+  caps.hll2 = hll_list2_cap(q.geom, q.rpb * q.blocks);
+  s.plan = plan_sketch_fold(q.state.hll_p, q.geom, caps);
   int rc;
-  if (s.hll_nsup && (rc = size_hll_level2(c, s, c->sk_pend.rpb * s.blocks))) return rc;
+  if ((rc = ensure_sketch_lists(c, s.plan, s.blocks, s.bufs))) return rc;
   Span sp;
   if ((rc = span_open(c, sp))) return rc;
   ENQ(c);
   ForkJoin fj{};
-  if (!c->cpu && (rc = fold_fork_join(c, &fj))) return rc;
-  HIPCHK(c, launch_sketch(s, c->stream, nullptr, c->cpu ? nullptr : &fj));
+  if ((rc = fold_fork_join(c, &fj))) return rc;
+  HIPCHK(c, launch_sketch(s, c->stream, &fj));
   return span_close(c, sp, c->pending_fold);
 }
 
@@ -1341,32 +1387,29 @@ int fold_pending_sketch(gpuagg_ctx *c) {
 // reads them); the HLL lists stay deferred, and later scatters append to count-min lists
 // that start empty again.
 int hh_fold_cms(gpuagg_ctx *c) {
-  if (!c->sk_pend.active) return GPUAGG_OK;
-  SketchArgs s = c->sk_pend.s;
-  if (!s.nwin || !s.cms_depth) return GPUAGG_OK;  // count-min updates were direct atomics
-  if (!s.hll_nsup || !s.hll_p) return fold_pending_sketch(c);  // nothing of HLL waits
-  s.passes = kSketchFolds;
-  s.accum = false;
-  s.hll_nsup = 0;  // launch_sketch: no HLL split / fold
+  const auto &q = c->sk_pend;
+  SketchPendingFacts pf;  // (plan_hh_fold reads nothing else)
+  pf.active = q.active;
+  pf.geom = q.geom;
+  const HhFold what = plan_hh_fold(pf);
+  if (what == HhFold::none) return GPUAGG_OK;
+  if (what == HhFold::whole) return fold_pending_sketch(c);
+  SketchArgs s = pending_sketch_args(c);
+  s.plan = plan_sketch_fold(q.state.hll_p, q.geom, q.caps, /*cms_only=*/true);
   ENQ(c);
-  HIPCHK(c, launch_sketch(s, c->stream, nullptr));
-  HIPCHK(c, x_set_async(c, s.counts, 0, (size_t)s.blocks * s.nwin * 4, c->stream));
+  HIPCHK(c, launch_sketch(s, c->stream));
+  HIPCHK(c, x_set_async(c, s.bufs.counts, 0, (size_t)s.blocks * q.geom.nwin * 4, c->stream));
   return GPUAGG_OK;
 }
 
-// The sketch pass over n records: count-min scatter + fold, HLL direct (SketchArgs).
+// The sketch pass over n records: gather the facts, plan, ensure the lists, launch, record
+// what waits.
 int launch_sketches(gpuagg_ctx *c, const ColsView &cv, size_t n) {
   int rc;
   SketchArgs s{};
+  static_cast<SketchState &>(s) = sketch_state(c);
   s.ip = ip_table(c);
-  s.cms = c->d_cms;
-  s.cms_depth = c->cms_len ? c->cfg.cms_depth : 0;
-  s.cms_wlog2 = c->cfg.cms_width_log2;
-  s.hll = c->d_hll;
-  s.hll_p = c->hll_len ? c->cfg.hll_precision : 0;
   s.blocks = c->n_cu;
-  s.win_shift = std::min<uint32_t>(kCmsWindowShift, s.cms_wlog2);
-  s.hll_slots = s.hll_p ? (uint32_t)(c->hll_len >> s.hll_p) : 0;
   if (c->cpu) {  // relaxed atomics on the shared rows / registers
     s.cols = ColsView{cv.src_ip, cv.dst_ip, nullptr, cv.meta, cv.ports, nullptr};
     s.n = n;
@@ -1374,126 +1417,51 @@ int launch_sketches(gpuagg_ctx *c, const ColsView &cv, size_t n) {
     if (c->hh_min) c->hh_cpu.pass(cv, n, c->d_cms, c->cfg.cms_depth, c->cfg.cms_width_log2, c->hh_min);
     return GPUAGG_OK;
   }
-  if (s.hll_p && c->ipl_all.bytes) s.ipl = c->ipl_all;
-  // HLL bucketing: fine windows of 2^hll_shift pods (128 KiB of registers, the fold's
-  // LDS), super-windows of 2^hll_sshift pods (~16 of them, the scatter's lists); pod bits
-  // of an entry: 26 - p
-  uint64_t hnwin = 0, hnsup = 0;
-  const bool direct = c->cfg.flags & GPUAGG_FLAG_DIRECT_SKETCH;
-  if (!direct && s.hll_p && s.hll_p <= kHllWindowLog2Bytes && s.hll_slots) {
-    s.hll_shift = std::min<uint32_t>(8u, kHllWindowLog2Bytes - s.hll_p);
-    uint32_t ss = s.hll_shift;
-    while ((((uint64_t)s.hll_slots + (1u << ss) - 1) >> ss) > 16 && ss < 26 - s.hll_p && ss < s.hll_shift + 10) ++ss;
-    s.hll_sshift = ss;
-    hnwin = ((uint64_t)s.hll_slots + (1u << s.hll_shift) - 1) >> s.hll_shift;
-    hnsup = ((uint64_t)s.hll_slots + (1u << ss) - 1) >> ss;
-    if (hnwin > kHllMaxWindows || hnsup > 1024) hnwin = hnsup = 0;
-    s.hll_b2 = (uint32_t)std::min<uint64_t>(64, std::max<uint64_t>(1, c->n_cu / std::max<uint64_t>(1, hnsup)));
-  }
-  const uint64_t nwin = s.cms_depth ? ((uint64_t)s.cms_depth << (s.cms_wlog2 - s.win_shift)) : 0;
-  const uint64_t per_launch = (uint64_t)s.blocks << 20;  // <= 2^20 records per scatter workgroup
-  // Lists sized for `rpb` records per scatter workgroup (one launch's chunk, or the deferral
-  // budget).  CMS: expected entries per list = rpb * depth / nwin, +12.5 % + 2048 of headroom;
-  // HLL level 1: at most one entry per record, rpb / nsup per list, +25 % + 64 (a full list
-  // falls back to the exact global atomic / CAS).
-  auto size_lists = [&](SketchArgs &x, uint64_t rpb) -> int {
-    int r;
-    x.nwin = 0;
-    if (!direct && nwin && nwin <= kCmsMaxWindows) {
-      const uint64_t mean = rpb * x.cms_depth / nwin;
-      const uint64_t cap = (mean + mean / 8 + 2048 + 7) & ~7ULL;
-      if ((r = c->d_sk_lists.ensure(c, (size_t)x.blocks * nwin * cap))) return r;
-      if ((r = c->d_sk_counts.ensure(c, (size_t)x.blocks * nwin))) return r;
-      x.nwin = (uint32_t)nwin;
-      x.cap = (uint32_t)cap;
-      x.lists = c->d_sk_lists;
-      x.counts = c->d_sk_counts;
-      x.fold_blocks = (uint32_t)nwin * std::max<uint32_t>(1u, c->n_cu / (uint32_t)nwin);
-    }
-    x.hll_nwin = x.hll_nsup = 0;
-    if (hnsup) {
-      const uint64_t mean = rpb / hnsup;
-      const uint64_t cap = (mean + mean / 4 + 64 + 15) & ~15ULL;
-      if ((r = c->d_hll_lists.ensure(c, (size_t)x.blocks * hnsup * cap))) return r;
-      if ((r = c->d_hll_counts.ensure(c, (size_t)x.blocks * hnsup))) return r;
-      x.hll_nsup = (uint32_t)hnsup;
-      x.hll_nwin = (uint32_t)hnwin;
-      x.hll_cap = (uint32_t)cap;
-      x.hll_lists = c->d_hll_lists;
-      x.hll_counts = c->d_hll_counts;
-    }
-    return GPUAGG_OK;
-  };
+  const SketchFacts f = sketch_facts(c, s);
+  const SketchGeom g = sketch_geom(f);
+  s.ipl = c->ipl_all;
   // Timing (gpuagg_set_timing): sketch_ms spans the scatter launches only -- the kernel
   // bench.py names -- and the folds count in fold_ms (fold_pending_sketch, or the pair
   // around a full-size launch's folds below); sketch_launches counts submits.
   if (c->timing) ++c->pending_sketch_submits;
-  // Deferred folds (small launches, e.g. the Go plugin's 2^20 records: chunk 4096): the
-  // folds' fixed passes -- every count-min row and the whole HLL register array (164 MB at
-  // C3's 10k pods, p = 14) are read and rewritten -- cost ~20x the scatter of such a launch,
-  // so launches keep appending to one set of lists sized for kSketchDeferRecords records per
-  // workgroup and fold_pending folds them once (gpuagg_sync, state reads, merge, relayout,
-  // or when the next launch would not fit).
-  const uint64_t chunk1 = ((std::min<uint64_t>(n, per_launch) + s.blocks - 1) / s.blocks + 3) & ~3ULL;
-  const bool defer = c->defer_folds && !direct && n <= per_launch && 2 * chunk1 <= kSketchDeferRecords &&
-                     (nwin || hnsup);
-  if (c->sk_pend.active) {
-    const SketchArgs &q = c->sk_pend.s;
-    const bool fits = defer && c->sk_pend.rpb + chunk1 <= c->sk_pend.budget && q.blocks == s.blocks &&
-                      q.cms == s.cms && q.hll == s.hll && q.hll_slots == s.hll_slots &&
-                      q.hll_shift == s.hll_shift && q.hll_sshift == s.hll_sshift && q.hll_b2 == s.hll_b2 &&
-                      q.lists == c->d_sk_lists && q.hll_lists == c->d_hll_lists;
-    if (!fits && (rc = fold_pending_sketch(c))) return rc;
-  }
-  for (uint64_t off = 0; off < n; off += per_launch) {
-    const uint64_t m = std::min<uint64_t>(per_launch, n - off);
+  const SketchSubmit sub = plan_sketch_submit(f, g, n, sketch_pending_facts(c, s));
+  if (sub.fold_first && (rc = fold_pending_sketch(c))) return rc;
+  for (uint64_t off = 0; off < n; off += sub.per_launch) {
+    const uint64_t m = std::min<uint64_t>(sub.per_launch, n - off);
     s.cols = ColsView{cv.src_ip + off, cv.dst_ip + off, nullptr, cv.meta + off,
                       cv.ports ? cv.ports + off : nullptr, nullptr};
     s.n = m;
-    s.chunk = ((m + s.blocks - 1) / s.blocks + 3) & ~3ULL;  // whole 4-record vectors
-    if (defer) {
-      const bool accum = c->sk_pend.active;
-      if (accum) {  // the waiting lists' geometry
-        const SketchArgs &q = c->sk_pend.s;
-        s.nwin = q.nwin;
-        s.cap = q.cap;
-        s.lists = q.lists;
-        s.counts = q.counts;
-        s.fold_blocks = q.fold_blocks;
-        s.hll_nsup = q.hll_nsup;
-        s.hll_nwin = q.hll_nwin;
-        s.hll_cap = q.hll_cap;
-        s.hll_lists = q.hll_lists;
-        s.hll_counts = q.hll_counts;
-      } else if ((rc = size_lists(s, kSketchDeferRecords))) {
-        return rc;
-      }
-      s.passes = kSketchScatter;
-      s.accum = accum;
-      ENQ(c);
-      Span ev;
-      if ((rc = span_open(c, ev))) return rc;
-      HIPCHK(c, launch_sketch(s, c->stream, &c->sketch_kernel_name));
-      if ((rc = span_close(c, ev, c->pending_sketch))) return rc;
-      c->sk_pend.rpb = (accum ? c->sk_pend.rpb : 0) + s.chunk;
-      c->sk_pend.budget = kSketchDeferRecords;
-      c->sk_pend.s = s;
-      c->sk_pend.active = true;
+    const uint32_t *cols[6] = {s.cols.src_ip, s.cols.dst_ip, nullptr, s.cols.meta, s.cols.ports, nullptr};
+    uint32_t aligned = 0;
+    for (int j = 0; j < 6; ++j) aligned |= (((uintptr_t)cols[j] & 15u) == 0) << j;
+    const SketchPlan p = plan_sketch_batch(f, g, sub, m, aligned);
+    if ((rc = ensure_sketch_lists(c, p, s.blocks, s.bufs))) return rc;
+    // the scatter, then its folds as a call of their own, so each is timed on its own
+    ENQ(c);
+    Span ev;
+    s.plan = scatter_only(p);
+    if ((rc = span_open(c, ev))) return rc;
+    HIPCHK(c, launch_sketch(s, c->stream));
+    if ((rc = span_close(c, ev, c->pending_sketch))) return rc;
+    char kname[64];
+    sketch_variant_name(p.variant, kname, sizeof kname);
+    c->sketch_kernel_name = kname;
+    if (sub.defer) {
+      auto &q = c->sk_pend;
+      q.rpb = (p.accum ? q.rpb : 0) + p.chunk;
+      q.budget = sub.budget;
+      q.geom = g;
+      q.caps = p.caps;
+      q.state = s;
+      q.bufs = s.bufs;
+      q.blocks = s.blocks;
+      q.active = true;
       continue;
     }
-    if ((rc = size_lists(s, s.chunk))) return rc;
-    if (hnsup && (rc = size_hll_level2(c, s, m))) return rc;
-    // the scatter, then its folds (kSketchBoth as two calls, so each is timed on its own)
-    s.accum = false;
-    ENQ(c);
-    Span ev, evf;
-    s.passes = kSketchScatter;
-    if ((rc = span_open(c, ev))) return rc;
-    HIPCHK(c, launch_sketch(s, c->stream, &c->sketch_kernel_name));
-    if ((rc = span_close(c, ev, c->pending_sketch))) return rc;
-    s.passes = kSketchFolds;
+    s.plan = folds_only(p);
+    Span evf;
     if ((rc = span_open(c, evf))) return rc;
-    HIPCHK(c, launch_sketch(s, c->stream, nullptr));
+    HIPCHK(c, launch_sketch(s, c->stream));
     if ((rc = span_close(c, evf, c->pending_fold))) return rc;
   }
   // heavy hitters: every record of this submit against the rows that now hold all of it

@@ -1,7 +1,8 @@
 """The small host-only C++ programs of the suite (tests/*.cpp that include the engine's headers),
 compiled with g++ once per process into a temporary directory: the launch planner
-(launch_plan_test.cpp; test_launch_plan.py, seglist_cases.py), key_hash (key_hash_test.cpp) and the
-heavy-hitter readout's hash slices (hh_hash_test.cpp; hh_cases.py)."""
+(launch_plan_test.cpp; test_launch_plan.py, seglist_cases.py), the sketch launch planner
+(sketch_plan_test.cpp; test_sketch_plan.py), key_hash (key_hash_test.cpp) and the heavy-hitter
+readout's hash slices (hh_hash_test.cpp; hh_cases.py)."""
 
 from __future__ import annotations
 
@@ -36,6 +37,10 @@ def build(name: str) -> str:
 
 def planner() -> str:
     return build("launch_plan_test")
+
+
+def sketch_planner() -> str:
+    return build("sketch_plan_test")
 
 
 def plan(exe: str, cases):

@@ -208,7 +208,7 @@ def narrow_rows(be: Backend, w: int):
 
 
 # ---- the staging rings do not fit ---------------------------------------------------------
-# stage_words (gpuagg_kernels.hip), w = 2^22, one HLL super-window: d = 4 gives 512 windows
+# stage_words (gpuagg_sketch_plan.h), w = 2^22, one HLL super-window: d = 4 gives 512 windows
 # with 128-entry rings, 4 * (1028 + 32772 + 8192 + 64) = 168,224 bytes at round 4 (> 160 KiB)
 # but 4 * (1028 + 32772 + 4096 + 64) = 151,840 bytes at round 2, which fits beside an IP
 # image of up to 12,000 bytes: that shape is the round-2 fallback, not the unstaged kernel.
@@ -316,8 +316,8 @@ OVERFLOW_N = 5 << 20
 
 
 def list_geometry(n: int, blocks: int, d: int, w: int, p: int, hll_slots: int):
-    """The list sizing of launch_sketches (gpuagg_runtime.cpp) under FLAG_FOLD_PER_BATCH,
-    restated: size_lists(s, s.chunk) with
+    """The list sizing of the sketch planner (gpuagg_sketch_plan.h) under FLAG_FOLD_PER_BATCH,
+    restated: sketch_geom and the capacities for one launch's chunk, with
       chunk   = ((n + B - 1) / B + 3) & ~3                       records per workgroup
       nwin    = d << (w - win_shift), win_shift = min(15, w)    count-min windows
       cap     = (mean + mean / 8 + 2048 + 7) & ~7,  mean = chunk * d / nwin

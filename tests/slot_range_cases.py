@@ -533,7 +533,7 @@ HLL_N = 20_000
 
 def hll_shape(p: int, rows: int, n: int, cus: int):
     """hshift and the number of fine windows beside sketch_cases.list_geometry; lists: what
-    launch_sketches decides (hnwin <= kHllMaxWindows and hnsup <= 1024)."""
+    sketch_geom (gpuagg_sketch_plan.h) decides (hnwin <= kHllMaxWindows and hnsup <= 1024)."""
     geo = K.list_geometry(n, cus, 1, 15, p, rows)  # (its count-min part is not used)
     geo["hshift"] = min(8, 17 - p)
     geo["hnwin"] = -(-rows >> geo["hshift"])
